@@ -7,6 +7,9 @@ all-reduce of the counters + checksum digest.  N ranks split ONE global workload
 by history shard (dist.rank_workflows: shard = hash(workflow) mod 16384, shard -> rank = shard mod N),
 so per-GPU work is fixed (weak scaling); value = events of all ranks / max-over-ranks wall time.
 
+A plain run measures that headline alone: set up, warm up, time the steps, write the outputs of the last
+timed step (``--dump-outputs DIR``), print the result line.  Everything below runs with ``--full`` only.
+
 Beside it, on every rank with the same shard split and timing rules (``configs``):
   config 3 -- 1.25M mixed histories per GPU (the per-GPU shard of the 10M x 8-GPU job),
   config 4 -- long-tail histories (Zipf lengths up to 50k events, continue-as-new every 10k),
@@ -16,7 +19,8 @@ N=1: the end-to-end figure from host buffers (pinned, chunked, overlapped, compa
 host-ingest rates (native decoder, flatten) and the CPU baseline (oracle on the host cores, config 2
 sample and BASELINE config 1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--headline-only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--headline-only] [--no-cpu-baseline] [--no-e2e] ...
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -35,7 +39,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 PROFILE_TRAFFIC = os.path.join(ROOT, "profiles", "traffic.json")
 PROFILE_TRAFFIC_CONFIGS = os.path.join(ROOT, "profiles", "traffic_configs.json")
-MAX_TIMED_STEPS = 512   # crr_timing ring size (capi.hip kRing)
+MAX_TIMED_STEPS = 512   # crr_timing ring size (capi.hip kRing): the launches of a region timed one by one
 
 
 def parse():
@@ -45,6 +49,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--workflows", type=int, default=1_000_000, help="config 2 workflows per GPU (1M)")
     p.add_argument("--activities", type=int, default=4, help="activities per workflow (k=4 -> 29 events)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: configs 3 / 4 / 5, replication, end to end, host ingest, CPU baseline, "
+                        "parity checks (the options below that skip a part of these apply with --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the rows of the last timed headline step as DIR/<name>.npy (float64; a fixed, seeded "
+                        "sample of the workflows, at most 64 MB in all)")
     p.add_argument("--headline-only", action="store_true", help="config 2 only (no configs 3/4, e2e, CPU)")
     p.add_argument("--config-steps", type=int, default=5, help="timed steps of the config 3 / 4 / replication lines")
     p.add_argument("--c3-workflows", type=int, default=1_250_000, help="config 3 mixed workflows per GPU")
@@ -62,10 +72,12 @@ def parse():
                    help="collective backend for N > 1 (nccl = RCCL; gloo: e.g. several ranks sharing one GPU)")
     p.add_argument("--device", type=int, default=-1, help="GPU of this rank (default LOCAL_RANK)")
     a = p.parse_args()
-    if a.steps > MAX_TIMED_STEPS or a.config_steps > MAX_TIMED_STEPS:
-        p.error(f"--steps / --config-steps: at most {MAX_TIMED_STEPS} launches are timed per region")
+    if a.config_steps > MAX_TIMED_STEPS:
+        p.error(f"--config-steps: at most {MAX_TIMED_STEPS} launches are timed per region")
     if a.steps < 1:
         p.error("--steps must be >= 1")
+    if not a.full:   # a plain run: the headline's own steps and nothing beside them
+        a.headline_only = a.no_cpu_baseline = a.no_e2e = True
     return a
 
 
@@ -121,7 +133,8 @@ class Ctx:
 
 def timed_steps(ctx, db, steps, warmup, per_step=None, before_step=None):
     """warmup, barrier + sync, K launches (HIP-event ring around each launch's fast group), sync +
-    barrier; returns (max-over-ranks wall seconds, per-launch fast-group ms)."""
+    barrier; returns (max-over-ranks wall seconds, per-launch fast-group ms).  The wall clock spans all K
+    launches; the ring holds the first MAX_TIMED_STEPS of them (a launch past it records no event pair)."""
     torch, eng = ctx.torch, ctx.eng
     stream = torch.cuda.current_stream()
     for _ in range(warmup):
@@ -153,8 +166,8 @@ def timed_steps(ctx, db, steps, warmup, per_step=None, before_step=None):
             wall += time.perf_counter() - t0
         ctx.barrier()
     ms = eng.timing_read()
-    if len(ms) != steps:
-        raise RuntimeError(f"timed {len(ms)} kernel launches, expected {steps}")
+    if len(ms) != min(steps, MAX_TIMED_STEPS):
+        raise RuntimeError(f"timed {len(ms)} kernel launches, expected {min(steps, MAX_TIMED_STEPS)}")
     return ctx.reduce([wall])[0], ms
 
 
@@ -166,6 +179,66 @@ def roofline(alg_bytes, kernel_ms, kernel, traffic=None):
         r["traffic_GBs"] = traffic / (kernel_ms * 1e-3) / 1e9
         r["traffic_frac"] = r["traffic_GBs"] / HBM_PEAK_GBS
     return r
+
+
+# ---- --dump-outputs ----------------------------------------------------------------------------------------
+DUMP_WORKFLOWS = 32768          # sampled workflows: 32768 x 52 columns x 8 B = 13.6 MB of exec rows
+DUMP_TABLE_BYTES = 6_000_000    # per live-row table (8 tables): at most 13.6 + 48 MB < 64 MB in all
+DUMP_SEED = 0xCAD0D0
+
+
+def as_f64_columns(a):
+    """A structured (or plain integer) array as float64 [rows, columns], exactly: fields in declaration
+    order without ``reserved``; a 64-bit field gives two columns, its low 32 bits (unsigned) then its high
+    32 bits (signed), every narrower field one."""
+    if a.dtype.names is None:
+        a = a.view(np.dtype([("v", a.dtype)]))
+    cols = []
+    for f in a.dtype.names:
+        if f == "reserved":
+            continue
+        v = a[f]
+        if v.dtype.itemsize == 8:
+            v = v.astype(np.int64)
+            cols += [(v & np.int64(0xFFFFFFFF)).astype(np.float64), (v >> np.int64(32)).astype(np.float64)]
+        else:
+            cols.append(v.astype(np.float64))
+    return np.stack(cols, axis=1) if cols else np.zeros((a.shape[0], 0))
+
+
+def dump_outputs(path, batch, res, digest=None):
+    """What a caller of the timed path receives (engine.download: the exec rows and every workflow's live
+    table rows), for a fixed seeded sample of the workflows in canonical workflow order, as float64
+    ``<path>/exec.npy`` and ``<path>/<table>.npy`` (columns: as_f64_columns of abi.EXEC_ROW and of the
+    table's row type; the tables' rows: the sampled workflows' live rows concatenated, cut at
+    DUMP_TABLE_BYTES; a table without a live row in the sample gets no file, its zero counts are in the
+    exec rows), and the step's digest as ``digest.npy``.  The same arguments give the same
+    workflows, hence the same files from two builds that compute the same rows."""
+    from cadence_amd import abi
+    os.makedirs(path, exist_ok=True)
+    n_wf = batch.n_wf
+    pick = np.arange(n_wf, dtype=np.int64)
+    if n_wf > DUMP_WORKFLOWS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_wf, DUMP_WORKFLOWS, replace=False)).astype(np.int64)
+    # canonical workflow -> device position
+    pos = pick if batch.perm is None else np.argsort(batch.perm, kind="stable")[pick]
+    np.save(os.path.join(path, "exec.npy"), as_f64_columns(res.exec[pos]))
+    strides = np.asarray(batch.wf_strides(), np.int64)
+    for name, dt, base_f, cap_f, n_f in abi.TABLES:
+        n = np.maximum(np.minimum(res.exec[n_f].astype(np.int64), batch.wf[cap_f].astype(np.int64))[pos], 0)
+        if name == "tasks" and not batch.emit_tasks:
+            n[:] = 0
+        tot = int(n.sum())
+        wf_idx = np.repeat(pos, n)
+        slot = np.arange(tot, dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+        idx = (batch.wf[base_f].astype(np.int64)[wf_idx] + slot * strides[wf_idx])[:DUMP_TABLE_BYTES // (8 * 2 * len(dt.names))]
+        out = os.path.join(path, name + ".npy")
+        if idx.size:
+            np.save(out, as_f64_columns(res.tables[name][idx]))
+        elif os.path.exists(out):   # no live rows in the sample: no file (nor an earlier run's)
+            os.remove(out)
+    if digest is not None:
+        np.save(os.path.join(path, "digest.npy"), as_f64_columns(np.asarray(digest, np.int64)))
 
 
 # ---- config 2 (headline) -------------------------------------------------------------------------------
@@ -191,12 +264,14 @@ def config2(ctx):
 
     wall, ms = timed_steps(ctx, db, args.steps, args.warmup, per_step=exchange if ctx.world > 1 else None)
     kernel_avg_ms = float(np.mean(ms))
+    res = eng.download(db)   # the rows the last timed step wrote
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, batch, res, eng.read_digest(db) if ctx.world == 1 else None)
     eng.launch(db)   # the reported digest: one more launch, reduced once
     if ctx.world > 1:
         cdist.all_reduce_digest(torch, ctx.dist, db.tensors["digest"])
     digest = eng.read_digest(db)
     tot_events, tot_wf = ctx.reduce([float(n_events), float(n_wf)], op="sum")
-    res = eng.download(db)
     tier = "replay_lds_small_kernel" if db.c_in.flags & abi.IN_LDS_SMALL else "replay_lds_kernel"
     tail = bool(db.c_in.flags & abi.IN_WAVE_TAIL) and db.c_in.wave_begin < db.n_wf
     emit = bool(db.c_in.flags & abi.IN_EMIT_TASKS)

@@ -7,7 +7,7 @@
 set -u
 R="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd "$R"; mkdir -p gpurun_out
-A="--steps 5 --warmup 1 --config-steps 3 --no-cpu-baseline --no-e2e --c4-workflows 200"
+A="--full --steps 5 --warmup 1 --config-steps 3 --no-cpu-baseline --no-e2e --c4-workflows 200"
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
   --master-port 29517 bench.py --gpus 2 --backend gloo --device 0 --workflows 400000 --c3-workflows 300000 \
   --c5-workflows 200000 $A > gpurun_out/multirank6_n2.json 2> gpurun_out/multirank6_n2.err || { tail -30 gpurun_out/multirank6_n2.err; exit 1; }

@@ -21,7 +21,7 @@ def main():
     if a.lib:
         os.environ["CRR_LIB_PATH"] = os.path.abspath(a.lib)
     import numpy as np
-    sys.argv = [sys.argv[0]]
+    sys.argv = [sys.argv[0], "--full"]
     import bench
     from cadence_amd import synth, synth_native
     from cadence_amd import dist as cdist

@@ -20,7 +20,7 @@ def main():
     p.add_argument("--wf", type=int, default=1_000_000)
     p.add_argument("--steps", type=int, default=3)
     a = p.parse_args()
-    sys.argv = [sys.argv[0], "--config-steps", str(a.steps)]
+    sys.argv = [sys.argv[0], "--full", "--config-steps", str(a.steps)]
     import bench
     from cadence_amd import ndc, synth_native
     from cadence_amd import dist as cdist
