@@ -8,7 +8,7 @@ import enum
 
 import numpy as np
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # common/constants.go:30-58
 FIRST_EVENT_ID = 1
@@ -260,6 +260,51 @@ NDC_RESULT = np.dtype([("status", "<i4"), ("action", "<i4"), ("branch_index", "<
                        ("is_rebuilt", "<i4"), ("branch_changed", "<i4")])
 NDC_APPEND, NDC_NEW_BRANCH, NDC_DUPLICATE = 0, 1, 2
 
+# ---- persisted mutable-state loader (include/cadence_load.h) ------------------------------------------
+STATE_EXECUTION, STATE_ACTIVITY, STATE_TIMER, STATE_CHILD, STATE_REQUEST_CANCEL, STATE_SIGNAL = range(6)
+STATE_BLOB = np.dtype([("kind", "<u4"), ("str_len", "<u4"), ("id", "<i8"), ("aux_time", "<i8"), ("str_off", "<u8")])
+STATE_WF = np.dtype([("blob_begin", "<u4"), ("blob_count", "<u4"), ("next_event_id", "<i8")])
+
+
+class LoadStatus(enum.IntEnum):
+    OK = 0
+    MALFORMED = 1
+    NESTED_ENCODING = 2
+    DUPLICATE_ID = 3
+    VERSION_HISTORIES = 4
+    EXECUTION_COUNT = 5
+    TOO_LARGE = 6
+
+
+LOAD_MAX_BLOBS = 4096                        # CRR_LOAD_MAX_BLOBS
+LOAD_FLAG_STICKY = 1
+LOAD_FLAG_MULTI_BRANCH = 2
+LOAD_T_TOKEN, LOAD_T_KEYS, LOAD_T_KEY_BYTES, LOAD_TABLES = 7, 8, 9, 10
+# the seven row tables of the dense loaded image, in crr_load_image.rows order
+LOAD_ROW_TABLES = ["act", "timer", "child", "rc", "sig", "vh", "rp"]
+GO_ZERO_TIME_NANOS = -6795364578871345152     # time.Time{}.UnixNano() (thrift_mapper.go zeroTimeNanos)
+INGEST_PAD = 32                               # CRR_INGEST_PAD
+SCRATCH_TOO_SMALL = -100                      # CRR_INGEST_SCRATCH_TOO_SMALL
+
+
+class CStateBatch(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_void_p), ("blob_off", ctypes.c_void_p), ("blob", ctypes.c_void_p),
+                ("wf", ctypes.c_void_p), ("strings", ctypes.c_void_p), ("n_blobs", ctypes.c_uint32),
+                ("n_wf", ctypes.c_uint32)]
+
+
+class CLoadSummary(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_int32), ("n_failed", ctypes.c_uint32), ("err_blob", ctypes.c_int64),
+                ("totals", ctypes.c_uint64 * LOAD_TABLES), ("staging", ctypes.c_uint64 * 2),
+                ("scratch_needed", ctypes.c_uint64), ("n_blobs", ctypes.c_uint32), ("n_wf", ctypes.c_uint32)]
+
+
+class CLoadImage(ctypes.Structure):
+    _fields_ = [("exec", ctypes.c_void_p), ("rows", ctypes.c_void_p * 7), ("offsets", ctypes.c_void_p),
+                ("tokens", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("key_len", ctypes.c_void_p),
+                ("key_bytes", ctypes.c_void_p), ("status", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -327,6 +372,9 @@ def check_layout(lib):
         got = lib.crr_sizeof(i)
         if got != dt.itemsize:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {got} vs numpy {dt.itemsize}")
-    for i, st in ((13, CInputs), (14, COutputs)):
+    for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize)):
+        if lib.crr_sizeof(i) != n:
+            raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
+    for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage)):
         if lib.crr_sizeof(i) != ctypes.sizeof(st):
             raise RuntimeError(f"ABI layout mismatch for {st.__name__}: C {lib.crr_sizeof(i)} vs ctypes {ctypes.sizeof(st)}")

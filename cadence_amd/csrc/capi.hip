@@ -5,6 +5,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "cadence_load.h"
 #include "cadence_replay.h"
 #include "stream_device.h"
 
@@ -251,6 +252,11 @@ size_t crr_sizeof(int which) {
     case 12: return sizeof(crr_task_row);
     case 13: return sizeof(crr_inputs);
     case 14: return sizeof(crr_outputs);
+    case 15: return sizeof(crr_state_blob);
+    case 16: return sizeof(crr_state_wf);
+    case 17: return sizeof(crr_state_batch);
+    case 18: return sizeof(crr_load_summary);
+    case 19: return sizeof(crr_load_image);
     default: return 0;
   }
 }

@@ -1,0 +1,863 @@
+// load_decode.h -- the persisted mutable-state decoder (include/cadence_load.h), written once for both
+// builds: load_states.cpp compiles it for the host (crr_load_states_host, the specification) and
+// load_kernel.hip for gfx950 (crr_load_states_plan).  The phases are plain functions over one scratch
+// buffer; a host loop or a kernel calls them per blob / per workflow, with a prefix scan between them:
+//
+//   parse_blob   per blob      a pending entry's sqlblobs struct -> its row image (Rec)
+//   count_wf     per workflow  the execution blob -> the exec row; nested VersionHistories / ResetPoints
+//                              walked once to validate and count; duplicate IDs; the workflow's status
+//   (scan A)                   rows per table, token bytes, key candidates -> exclusive offsets
+//   emit_wf      per workflow  rows into the dense tables at their rank by ID, keys interned in blob order,
+//                              CRR_ROW_MAPPED, version-history items, token bytes, reset points
+//   (scan B)                   dictionary entries and bytes
+//   dict_wf      per workflow  the dictionary's key_off / key_len / bytes
+//
+// Wire format: thrift binary (big-endian; field header = type byte + i16 id, 0 ends a struct), field IDs of
+// .gen/go/sqlblobs/sqlblobs.go restated below (tests/golden/sqlblobs_fields.json pins them); a field whose
+// wire type is not the expected one is skipped like an unknown one, as thriftrw's FromWire does.
+// Every read is checked against the blob's end: a cursor that would pass it marks the reader bad, which
+// ends the blob with CRR_LOAD_MALFORMED.
+#ifndef CADENCE_LOAD_DECODE_H_
+#define CADENCE_LOAD_DECODE_H_
+
+#include <stdint.h>
+#include <string.h>
+
+#include "cadence_load.h"
+
+#if defined(__HIPCC__)
+#define CRR_HD __host__ __device__ inline
+#else
+#define CRR_HD inline
+#endif
+
+namespace crr_load {
+
+// time.Time{}.UnixNano() (serialization/thrift_mapper.go:702, zeroTimeNanos): timeFromUnixNano maps it back
+// to the zero time, which rows hold as CRR_ZERO_TIME
+constexpr int64_t kGoZeroTimeNanos = -6795364578871345152LL;
+constexpr uint64_t kInStrings = 1ull << 63;  // string offset: into crr_state_batch.strings, not .bytes
+
+// counters per workflow, scanned in place to exclusive offsets ([t][n_wf] = the total); 0..9 are the image's
+// offsets (CRR_LOAD_T_*), 10 / 11 the staging of key candidates (an upper bound of the dictionary)
+constexpr int kCand = 10, kCandBytes = 11, kCounters = 12;
+constexpr uint32_t kRowBytes[7] = {sizeof(crr_activity_row), sizeof(crr_timer_row), sizeof(crr_child_row),
+                                   sizeof(crr_initiated_row), sizeof(crr_initiated_row), sizeof(crr_vh_item),
+                                   sizeof(crr_reset_point_row)};
+
+// thrift binary type bytes
+enum : uint8_t { T_STOP = 0, T_BOOL = 2, T_BYTE = 3, T_DOUBLE = 4, T_I16 = 6, T_I32 = 8, T_I64 = 10, T_STRING = 11,
+                 T_STRUCT = 12, T_MAP = 13, T_SET = 14, T_LIST = 15 };
+
+// ---- bounds-checked reader --------------------------------------------------------------------------------
+struct Rd {
+  const uint8_t* p;
+  uint64_t pos, end;  // pos <= end always
+  bool bad;
+};
+
+CRR_HD bool need(Rd& r, uint64_t n) {
+  if (r.bad || n > r.end - r.pos) {
+    r.bad = true;
+    return false;
+  }
+  return true;
+}
+CRR_HD uint8_t rd_u8(Rd& r) {
+  if (!need(r, 1)) return 0;
+  return r.p[r.pos++];
+}
+CRR_HD int16_t rd_i16(Rd& r) {
+  if (!need(r, 2)) return 0;
+  const uint16_t v = (uint16_t)((r.p[r.pos] << 8) | r.p[r.pos + 1]);
+  r.pos += 2;
+  return (int16_t)v;
+}
+CRR_HD int32_t rd_i32(Rd& r) {
+  if (!need(r, 4)) return 0;
+  uint32_t v;
+  memcpy(&v, r.p + r.pos, 4);
+  r.pos += 4;
+  return (int32_t)__builtin_bswap32(v);
+}
+CRR_HD int64_t rd_i64(Rd& r) {
+  if (!need(r, 8)) return 0;
+  uint64_t v;
+  memcpy(&v, r.p + r.pos, 8);
+  r.pos += 8;
+  return (int64_t)__builtin_bswap64(v);
+}
+// thriftrw's binary reader rejects a bool byte other than 0 / 1
+CRR_HD bool rd_bool(Rd& r) {
+  const uint8_t b = rd_u8(r);
+  if (b > 1) r.bad = true;
+  return b == 1;
+}
+CRR_HD bool rd_str(Rd& r, uint64_t& off, uint32_t& len) {
+  const int32_t n = rd_i32(r);
+  off = r.pos;
+  len = 0;
+  if (r.bad) return false;
+  if (n < 0 || !need(r, (uint64_t)n)) {
+    r.bad = true;
+    return false;
+  }
+  len = (uint32_t)n;
+  r.pos += (uint64_t)n;
+  return true;
+}
+
+// Skipping a value of any type without recursion: containers push a frame; nesting past kMaxDepth (the
+// persisted structs nest two deep: list<string>, map<string, binary>) is reported as malformed.
+constexpr int kMaxDepth = 8;
+struct Frame {
+  uint32_t remaining;
+  uint8_t mode, t1, t2, pad;  // mode 0 struct, 1 list / set (t1 element), 2 map (t1 key, t2 value)
+};
+
+CRR_HD void skip(Rd& r, uint8_t t, Frame* stk) {
+  int sp = 0;
+  uint8_t cur = t;
+  bool have = true;
+  for (;;) {
+    if (r.bad) return;
+    if (have) {
+      have = false;
+      Frame f = {0, 0, 0, 0, 0};
+      bool push = false;
+      switch (cur) {
+        case T_BOOL: case T_BYTE: if (need(r, 1)) r.pos += 1; break;
+        case T_I16: if (need(r, 2)) r.pos += 2; break;
+        case T_I32: if (need(r, 4)) r.pos += 4; break;
+        case T_DOUBLE: case T_I64: if (need(r, 8)) r.pos += 8; break;
+        case T_STRING: {
+          uint64_t o;
+          uint32_t l;
+          rd_str(r, o, l);
+          break;
+        }
+        case T_STRUCT: push = true; break;
+        case T_SET: case T_LIST: {
+          f.mode = 1;
+          f.t1 = rd_u8(r);
+          const int32_t n = rd_i32(r);
+          // every element takes at least one byte: a count past the blob's end is malformed
+          if (n < 0 || (uint64_t)n > r.end - r.pos) r.bad = true;
+          f.remaining = (uint32_t)n;
+          push = true;
+          break;
+        }
+        case T_MAP: {
+          f.mode = 2;
+          f.t1 = rd_u8(r);
+          f.t2 = rd_u8(r);
+          const int32_t n = rd_i32(r);
+          if (n < 0 || 2 * (uint64_t)n > r.end - r.pos) r.bad = true;
+          f.remaining = 2u * (uint32_t)n;
+          push = true;
+          break;
+        }
+        default: r.bad = true;
+      }
+      if (push && !r.bad) {
+        if (sp == kMaxDepth) {
+          r.bad = true;
+          return;
+        }
+        stk[sp++] = f;
+      }
+      continue;
+    }
+    if (sp == 0) return;
+    Frame& f = stk[sp - 1];
+    if (f.mode == 0) {
+      const uint8_t ft = rd_u8(r);
+      if (r.bad) return;
+      if (ft == T_STOP) {
+        --sp;
+        continue;
+      }
+      rd_i16(r);
+      cur = ft;
+      have = true;
+    } else if (f.remaining == 0) {
+      --sp;
+    } else {
+      cur = (f.mode == 2 && (f.remaining & 1u)) ? f.t2 : f.t1;  // 2n left: a key next
+      --f.remaining;
+      have = true;
+    }
+  }
+}
+
+CRR_HD bool next_field(Rd& r, uint8_t& t, int16_t& id) {
+  t = rd_u8(r);
+  if (r.bad || t == T_STOP) return false;
+  id = rd_i16(r);
+  return !r.bad;
+}
+
+CRR_HD int64_t from_unix_nano(int64_t v) { return v == kGoZeroTimeNanos ? CRR_ZERO_TIME : v; }
+
+// ---- scratch layout ---------------------------------------------------------------------------------------
+// a pending entry's parsed blob: its row image (src / key fields set by emit_wf) and where its key string is
+struct Rec {
+  int64_t id;        // the ID its map is keyed and ordered by
+  uint64_t str_off;  // ActivityID (in bytes) / timer_id (kInStrings | offset in strings)
+  uint32_t str_len;
+  int32_t bad;       // the blob is malformed
+  union {
+    crr_activity_row act;
+    crr_timer_row timer;
+    crr_child_row child;
+    crr_initiated_row init;
+  } row;
+};
+
+// what count_wf learnt about the execution blob's nested blobs (absolute offsets into bytes)
+struct ExecAux {
+  uint64_t vh_off, rp_off;
+  uint32_t vh_len, rp_len;
+  int32_t exec_idx;   // index of the execution blob within the workflow
+  int32_t current;    // current version-history index
+};
+
+CRR_HD uint64_t align16(uint64_t x) { return (x + 15u) & ~15ull; }
+
+struct Layout {
+  uint64_t rec, aux, cnt, status, flags, err, exec, fixed_end;  // fixed part
+  uint64_t rows[7], tokens, cand_off, cand_len, key_off, key_len, key_bytes, end;  // sized by scan A's totals
+};
+
+// `tot`: scan A's totals indexed like the counters (0..7, kCand, kCandBytes used); NULL: the fixed part only
+inline Layout carve(uint32_t n_blobs, uint32_t n_wf, const uint64_t* tot) {
+  Layout L;
+  memset(&L, 0, sizeof L);
+  uint64_t o = 0;
+  L.rec = o;     o = align16(o + (uint64_t)n_blobs * sizeof(Rec));
+  L.aux = o;     o = align16(o + (uint64_t)n_wf * sizeof(ExecAux));
+  L.cnt = o;     o = align16(o + (uint64_t)kCounters * ((uint64_t)n_wf + 1) * sizeof(int64_t));
+  L.status = o;  o = align16(o + (uint64_t)n_wf * sizeof(int32_t));
+  L.flags = o;   o = align16(o + (uint64_t)n_wf * sizeof(uint32_t));
+  L.err = o;     o = align16(o + (3 + kCounters) * sizeof(uint64_t));
+  L.exec = o;    o = align16(o + (uint64_t)n_wf * sizeof(crr_exec_row));
+  L.fixed_end = o;
+  if (tot) {
+    for (int t = 0; t < 7; ++t) { L.rows[t] = o; o = align16(o + tot[t] * kRowBytes[t]); }
+    L.tokens = o;    o = align16(o + tot[CRR_LOAD_T_TOKEN]);
+    L.cand_off = o;  o = align16(o + tot[kCand] * sizeof(uint64_t));
+    L.cand_len = o;  o = align16(o + tot[kCand] * sizeof(uint32_t));
+    L.key_off = o;   o = align16(o + tot[kCand] * sizeof(uint64_t));
+    L.key_len = o;   o = align16(o + tot[kCand] * sizeof(uint32_t));
+    L.key_bytes = o; o = align16(o + tot[kCandBytes]);
+  }
+  L.end = o;
+  return L;
+}
+
+struct Ctx {
+  crr_state_batch in;
+  uint8_t* s;  // the scratch
+  Layout L;
+  CRR_HD Rec* rec() const { return reinterpret_cast<Rec*>(s + L.rec); }
+  CRR_HD ExecAux* aux() const { return reinterpret_cast<ExecAux*>(s + L.aux); }
+  CRR_HD int64_t* cnt(int t) const { return reinterpret_cast<int64_t*>(s + L.cnt) + (uint64_t)t * ((uint64_t)in.n_wf + 1); }
+  CRR_HD int32_t* status() const { return reinterpret_cast<int32_t*>(s + L.status); }
+  CRR_HD uint32_t* flags() const { return reinterpret_cast<uint32_t*>(s + L.flags); }
+  CRR_HD uint64_t* err() const { return reinterpret_cast<uint64_t*>(s + L.err); }  // [0] lowest malformed blob, [1] failed, [2..] totals, [2 + kCounters] bad ranges
+  CRR_HD crr_exec_row* exec() const { return reinterpret_cast<crr_exec_row*>(s + L.exec); }
+  CRR_HD uint8_t* rows(int t) const { return s + L.rows[t]; }
+  CRR_HD uint8_t* tokens() const { return s + L.tokens; }
+  CRR_HD uint64_t* cand_off() const { return reinterpret_cast<uint64_t*>(s + L.cand_off); }
+  CRR_HD uint32_t* cand_len() const { return reinterpret_cast<uint32_t*>(s + L.cand_len); }
+  CRR_HD uint64_t* key_off() const { return reinterpret_cast<uint64_t*>(s + L.key_off); }
+  CRR_HD uint32_t* key_len() const { return reinterpret_cast<uint32_t*>(s + L.key_len); }
+  CRR_HD uint8_t* key_bytes() const { return s + L.key_bytes; }
+  CRR_HD const uint8_t* str(uint64_t off) const { return (off & kInStrings) ? in.strings + (off & ~kInStrings) : in.bytes + off; }
+  CRR_HD Rd blob(uint32_t b) const {
+    Rd r = {in.bytes, in.blob_off[b], in.blob_off[b + 1], false};
+    if (r.end < r.pos || r.end > in.blob_off[in.n_blobs]) {   // offsets not ascending within the batch's bytes
+      r.end = r.pos;
+      r.bad = true;
+    }
+    return r;
+  }
+};
+
+CRR_HD void note_malformed(const Ctx& c, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicMin(reinterpret_cast<unsigned long long*>(c.err()), (unsigned long long)b);
+#else
+  uint64_t* p = c.err();
+  uint64_t cur = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (b < cur && !__atomic_compare_exchange_n(p, &cur, b, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+#endif
+}
+CRR_HD void note_failed(const Ctx& c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicAdd(reinterpret_cast<unsigned long long*>(c.err() + 1), 1ull);
+#else
+  __atomic_fetch_add(c.err() + 1, 1ull, __ATOMIC_RELAXED);
+#endif
+}
+
+// ---- pending entries: sqlblobs.ActivityInfo / TimerInfo / ChildExecutionInfo / RequestCancelInfo / SignalInfo
+#define CRR_F(ID, TYPE, STMT) \
+  case ID:                    \
+    if (t == TYPE) {          \
+      STMT;                   \
+    } else {                  \
+      skip(r, t, stk);        \
+    }                         \
+    break;
+
+CRR_HD void parse_blob(const Ctx& c, uint32_t b, Frame* stk) {
+  const crr_state_blob B = c.in.blob[b];
+  Rec o;
+  memset(&o, 0, sizeof o);
+  o.id = B.id;
+  if (B.kind == CRR_STATE_EXECUTION || B.kind > CRR_STATE_SIGNAL) {  // execution blobs: count_wf
+    o.bad = B.kind > CRR_STATE_SIGNAL;
+    c.rec()[b] = o;
+    return;
+  }
+  Rd r = c.blob(b);
+  uint8_t t;
+  int16_t id;
+  if (B.kind == CRR_STATE_ACTIVITY) {
+    crr_activity_row& a = o.row.act;   // absent fields: the Go getters' zero values (times: Unix 0)
+    a.schedule_id = B.id;
+    a.flags = CRR_ROW_LIVE;
+    a.last_heartbeat_time = from_unix_nano(B.aux_time);
+    while (next_field(r, t, id)) {
+      switch (id) {
+        CRR_F(10, T_I64, a.version = rd_i64(r))
+        CRR_F(12, T_I64, a.scheduled_batch_id = rd_i64(r))
+        CRR_F(18, T_I64, a.scheduled_time = from_unix_nano(rd_i64(r)))
+        CRR_F(20, T_I64, a.started_id = rd_i64(r))
+        CRR_F(26, T_I64, a.started_time = from_unix_nano(rd_i64(r)))
+        CRR_F(28, T_STRING, rd_str(r, o.str_off, o.str_len))
+        CRR_F(32, T_I32, a.schedule_to_start = rd_i32(r))
+        CRR_F(34, T_I32, a.schedule_to_close = rd_i32(r))
+        CRR_F(36, T_I32, a.start_to_close = rd_i32(r))
+        CRR_F(38, T_I32, a.heartbeat = rd_i32(r))
+        CRR_F(40, T_BOOL, a.flags = (a.flags & ~CRR_ROW_CANCEL_REQUESTED) | (rd_bool(r) ? CRR_ROW_CANCEL_REQUESTED : 0u))
+        CRR_F(42, T_I64, a.cancel_request_id = rd_i64(r))
+        CRR_F(44, T_I32, a.timer_task_status = rd_i32(r))
+        CRR_F(46, T_I32, a.attempt = rd_i32(r))
+        CRR_F(52, T_BOOL, a.flags = (a.flags & ~CRR_ROW_HAS_RETRY) | (rd_bool(r) ? CRR_ROW_HAS_RETRY : 0u))
+        default: skip(r, t, stk);
+      }
+    }
+  } else if (B.kind == CRR_STATE_TIMER) {
+    crr_timer_row& m = o.row.timer;
+    m.flags = CRR_ROW_LIVE;
+    o.str_off = kInStrings | B.str_off;
+    o.str_len = B.str_len;
+    while (next_field(r, t, id)) {
+      switch (id) {
+        CRR_F(10, T_I64, m.version = rd_i64(r))
+        CRR_F(12, T_I64, m.started_id = rd_i64(r))
+        CRR_F(14, T_I64, m.expiry_time = from_unix_nano(rd_i64(r)))
+        CRR_F(16, T_I64, m.task_status = (int32_t)rd_i64(r))   // TaskID carries TaskStatus (workflowStateMaps.go:296-299)
+        default: skip(r, t, stk);
+      }
+    }
+    o.id = m.started_id;
+  } else if (B.kind == CRR_STATE_CHILD) {
+    crr_child_row& m = o.row.child;
+    m.initiated_id = B.id;
+    m.flags = CRR_ROW_LIVE;
+    while (next_field(r, t, id)) {
+      switch (id) {
+        CRR_F(10, T_I64, m.version = rd_i64(r))
+        CRR_F(12, T_I64, m.initiated_batch_id = rd_i64(r))
+        CRR_F(14, T_I64, m.started_id = rd_i64(r))
+        default: skip(r, t, stk);
+      }
+    }
+  } else {  // RequestCancelInfo / SignalInfo: the same two numeric fields
+    crr_initiated_row& m = o.row.init;
+    m.initiated_id = B.id;
+    m.flags = CRR_ROW_LIVE;
+    while (next_field(r, t, id)) {
+      switch (id) {
+        CRR_F(10, T_I64, m.version = rd_i64(r))
+        CRR_F(11, T_I64, m.initiated_batch_id = rd_i64(r))
+        default: skip(r, t, stk);
+      }
+    }
+  }
+  o.bad = r.bad;
+  c.rec()[b] = o;
+}
+
+// ---- nested DataBlobs ---------------------------------------------------------------------------------------
+CRR_HD bool str_is(const uint8_t* p, uint32_t len, const char* lit, uint32_t n) {
+  if (len != n) return false;
+  for (uint32_t i = 0; i < n; ++i)
+    if (p[i] != (uint8_t)lit[i]) return false;
+  return true;
+}
+
+struct VhWalk {
+  int32_t current;     // CurrentVersionHistoryIndex (absent: 0)
+  int32_t n_hist;
+  int32_t n_items;     // of history `target`
+  uint64_t tok_off;    // its branch token
+  uint32_t tok_len;
+};
+
+// shared.VersionHistories{10 currentVersionHistoryIndex, 20 list<VersionHistory{10 branchToken,
+// 20 list<VersionHistoryItem{10 eventID, 20 version}>}>} behind the 0x59 preamble; items of history `target`
+// go to `items` (NULL: counted only).  false: malformed (a repeated list field included, so that every
+// index written here stays below the count an earlier walk returned).
+CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame* stk) {
+  out.current = 0;
+  out.n_hist = 0;
+  out.n_items = 0;
+  out.tok_off = 0;
+  out.tok_len = 0;
+  if (rd_u8(r) != 0x59) return false;
+  uint8_t t, t2, t3;
+  int16_t id, id2, id3;
+  bool seen_histories = false;
+  while (next_field(r, t, id)) {
+    if (id == 10 && t == T_I32) {
+      out.current = rd_i32(r);
+    } else if (id == 20 && t == T_LIST) {
+      if (seen_histories) return false;   // thriftrw never writes a field twice: a repeated list is malformed
+      seen_histories = true;
+      const uint8_t et = rd_u8(r);
+      const int32_t n = rd_i32(r);
+      if (r.bad || et != T_STRUCT || n < 0 || (uint64_t)n > r.end - r.pos) return false;
+      for (int32_t h = 0; h < n; ++h) {
+        const bool mine = out.n_hist == target;
+        bool seen_items = false;
+        while (next_field(r, t2, id2)) {
+          if (id2 == 10 && t2 == T_STRING) {
+            uint64_t o;
+            uint32_t l;
+            rd_str(r, o, l);
+            if (mine) {
+              out.tok_off = o;
+              out.tok_len = l;
+            }
+          } else if (id2 == 20 && t2 == T_LIST) {
+            const uint8_t et2 = rd_u8(r);
+            const int32_t m = rd_i32(r);
+            if (r.bad || seen_items || et2 != T_STRUCT || m < 0 || (uint64_t)m > r.end - r.pos) return false;
+            seen_items = true;
+            for (int32_t k = 0; k < m; ++k) {
+              crr_vh_item it = {0, 0};
+              while (next_field(r, t3, id3)) {
+                if (id3 == 10 && t3 == T_I64) it.event_id = rd_i64(r);
+                else if (id3 == 20 && t3 == T_I64) it.version = rd_i64(r);
+                else skip(r, t3, stk);
+              }
+              if (r.bad) return false;
+              if (mine) {
+                if (items) items[out.n_items] = it;
+                ++out.n_items;
+              }
+            }
+          } else {
+            skip(r, t2, stk);
+          }
+        }
+        if (r.bad) return false;
+        ++out.n_hist;
+      }
+    } else {
+      skip(r, t, stk);
+    }
+  }
+  return !r.bad;
+}
+
+// shared.ResetPoints{10 list<ResetPointInfo{10 binaryChecksum, 20 runID, 30 firstDecisionCompletedID,
+// 40 createdTimeNano, 50 expiringTimeNano, 60 resettable}>} behind the 0x59 preamble.  `F(index, checksum
+// offset, length, resettable)` is called per point.  false: malformed.
+template <class Fn>
+CRR_HD bool walk_reset_points(Rd r, Frame* stk, Fn&& fn) {
+  if (rd_u8(r) != 0x59) return false;
+  uint8_t t, t2;
+  int16_t id, id2;
+  bool seen_points = false;
+  while (next_field(r, t, id)) {
+    if (id == 10 && t == T_LIST) {
+      if (seen_points) return false;   // as in walk_vh: so the count pass and the emit pass see one list
+      seen_points = true;
+      const uint8_t et = rd_u8(r);
+      const int32_t n = rd_i32(r);
+      if (r.bad || et != T_STRUCT || n < 0 || (uint64_t)n > r.end - r.pos) return false;
+      for (int32_t k = 0; k < n; ++k) {
+        uint64_t off = 0;
+        uint32_t len = 0;
+        bool resettable = false;
+        while (next_field(r, t2, id2)) {
+          if (id2 == 10 && t2 == T_STRING) rd_str(r, off, len);
+          else if (id2 == 60 && t2 == T_BOOL) resettable = rd_bool(r);
+          else skip(r, t2, stk);
+        }
+        if (r.bad) return false;
+        fn(k, off, len, resettable);
+      }
+    } else {
+      skip(r, t, stk);
+    }
+  }
+  return !r.bad;
+}
+
+// ---- per workflow: the execution blob, the counts, the status ---------------------------------------------
+struct ExecParse {
+  uint64_t vh_enc_off, rp_enc_off;
+  uint32_t vh_enc_len, rp_enc_len;
+  bool sticky;
+};
+
+// sqlblobs.WorkflowExecutionInfo -> the exec row (persistence_mapper.go ToInternalWorkflowExecutionInfo)
+CRR_HD bool parse_execution(Rd& r, Frame* stk, int32_t idx, crr_exec_row& R, ExecAux& A, ExecParse& P) {
+  uint8_t t;
+  int16_t id;
+  R.fail_step = -1;
+  R.completion_event_batch_id = CRR_EMPTY_EVENT_ID;   // persistence_mapper.go:32, kept when the field is absent
+  R.current_version = CRR_EMPTY_VERSION;              // Load, mutable_state_builder.go:325
+  R.flags = CRR_EXEC_RESET_POINTS_SET;                // DeserializeResetPoints never returns nil (serializer.go:144-148)
+  R.decision_request_src = CRR_SRC_NONE;
+  R.start_src = idx;
+  while (next_field(r, t, id)) {
+    switch (id) {
+      CRR_F(18, T_I64, R.completion_event_batch_id = rd_i64(r))
+      CRR_F(30, T_I32, R.decision_start_to_close = rd_i32(r))
+      CRR_F(34, T_I32, R.state = rd_i32(r))
+      CRR_F(36, T_I32, R.close_status = rd_i32(r))
+      CRR_F(48, T_I64, R.last_event_task_id = rd_i64(r))
+      CRR_F(50, T_I64, R.last_first_event_id = rd_i64(r))
+      CRR_F(52, T_I64, R.last_processed_event = rd_i64(r))
+      CRR_F(58, T_I64, R.decision_version = rd_i64(r))
+      CRR_F(60, T_I64, R.decision_schedule_id = rd_i64(r))
+      CRR_F(62, T_I64, R.decision_started_id = rd_i64(r))
+      CRR_F(64, T_I32, R.decision_timeout = rd_i32(r))
+      CRR_F(66, T_I64, R.decision_attempt = rd_i64(r))
+      CRR_F(68, T_I64, R.decision_started_ts = from_unix_nano(rd_i64(r)))
+      CRR_F(69, T_I64, R.decision_scheduled_ts = from_unix_nano(rd_i64(r)))
+      CRR_F(70, T_BOOL, R.flags = (R.flags & ~CRR_EXEC_CANCEL_REQUESTED) | (rd_bool(r) ? CRR_EXEC_CANCEL_REQUESTED : 0u))
+      CRR_F(71, T_I64, R.decision_orig_scheduled_ts = from_unix_nano(rd_i64(r)))
+      case 74:
+        if (t == T_STRING) {
+          uint64_t o;
+          uint32_t l;
+          if (rd_str(r, o, l))
+            R.decision_request_src = l == 0 ? CRR_SRC_NONE : (str_is(r.p + o, l, "emptyUuid", 9) ? CRR_SRC_EMPTY_UUID : idx);
+        } else {
+          skip(r, t, stk);
+        }
+        break;
+      case 78:
+        if (t == T_STRING) {
+          uint64_t o;
+          uint32_t l;
+          if (rd_str(r, o, l)) P.sticky = l != 0;
+        } else {
+          skip(r, t, stk);
+        }
+        break;
+      case 94:   // ExpirationTime: 0 in the row when unset or the zero time
+        if (t == T_I64) {
+          const int64_t v = rd_i64(r);
+          R.expiration_ns = v == kGoZeroTimeNanos ? 0 : v;
+        } else {
+          skip(r, t, stk);
+        }
+        break;
+      CRR_F(106, T_I64, R.signal_count = (int32_t)rd_i64(r))
+      CRR_F(115, T_STRING, rd_str(r, A.rp_off, A.rp_len))
+      CRR_F(116, T_STRING, rd_str(r, P.rp_enc_off, P.rp_enc_len))
+      CRR_F(122, T_STRING, rd_str(r, A.vh_off, A.vh_len))
+      CRR_F(124, T_STRING, rd_str(r, P.vh_enc_off, P.vh_enc_len))
+      default: skip(r, t, stk);
+    }
+  }
+  return !r.bad;
+}
+#undef CRR_F
+
+CRR_HD bool bytes_equal(const uint8_t* a, const uint8_t* b, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (a[i] != b[i]) return false;
+  return true;
+}
+
+// the workflows' blob ranges are consecutive and cover the blobs (cadence_load.h): checked per workflow against
+// its predecessor, so the device plan refuses the batches the host entry point refuses
+CRR_HD bool range_ok(const Ctx& c, uint32_t w) {
+  const crr_state_wf W = c.in.wf[w];
+  const uint64_t begin = w ? (uint64_t)c.in.wf[w - 1].blob_begin + c.in.wf[w - 1].blob_count : 0;
+  if (W.blob_begin != begin) return false;
+  return w + 1 < c.in.n_wf || (uint64_t)W.blob_begin + W.blob_count == c.in.n_blobs;
+}
+
+CRR_HD void count_wf(const Ctx& c, uint32_t w, Frame* stk) {
+  const crr_state_wf W = c.in.wf[w];
+  const uint32_t b0 = W.blob_begin;
+  const uint32_t n = (uint64_t)b0 + W.blob_count <= c.in.n_blobs ? W.blob_count : 0;   // a range outside the batch: no blobs
+  crr_exec_row R;
+  memset(&R, 0, sizeof R);
+  ExecAux A;
+  memset(&A, 0, sizeof A);
+  ExecParse P;
+  memset(&P, 0, sizeof P);
+  int64_t cnt[kCounters];
+  for (int t = 0; t < kCounters; ++t) cnt[t] = 0;
+  int32_t n_exec = 0;
+  bool malformed = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t k = c.in.blob[b0 + i].kind;
+    if (k == CRR_STATE_EXECUTION) {
+      ++n_exec;
+      A.exec_idx = (int32_t)i;
+    } else {
+      const Rec& rc = c.rec()[b0 + i];
+      if (rc.bad) {
+        malformed = true;
+        note_malformed(c, b0 + i);
+      } else {
+        ++cnt[k - 1];
+        if (k == CRR_STATE_ACTIVITY || k == CRR_STATE_TIMER) {
+          ++cnt[kCand];
+          cnt[kCandBytes] += rc.str_len;
+        }
+      }
+    }
+  }
+  int32_t st = CRR_LOAD_OK;
+  uint32_t fl = 0;
+  if (W.blob_count > CRR_LOAD_MAX_BLOBS) st = CRR_LOAD_TOO_LARGE;
+  else if (n_exec != 1) st = CRR_LOAD_EXECUTION_COUNT;
+  VhWalk V;
+  memset(&V, 0, sizeof V);
+  if (st == CRR_LOAD_OK) {
+    const uint32_t eb = b0 + (uint32_t)A.exec_idx;
+    Rd r = c.blob(eb);
+    bool ok = parse_execution(r, stk, A.exec_idx, R, A, P);
+    bool enc_ok = true, vh_ok = true;
+    if (ok && A.vh_len) {   // an empty nested blob: the field is absent
+      if (!str_is(r.p + P.vh_enc_off, P.vh_enc_len, "thriftrw", 8)) enc_ok = false;
+      else {
+        Rd v = {c.in.bytes, A.vh_off, A.vh_off + A.vh_len, false};
+        VhWalk V0;
+        ok = walk_vh(v, -1, nullptr, V0, stk);
+        if (ok) {
+          if (V0.n_hist == 0 || V0.current < 0 || V0.current >= V0.n_hist) vh_ok = false;
+          else ok = walk_vh(v, V0.current, nullptr, V, stk);
+        }
+      }
+    } else if (ok) {
+      vh_ok = false;
+    }
+    if (ok && A.rp_len) {
+      if (!str_is(r.p + P.rp_enc_off, P.rp_enc_len, "thriftrw", 8)) enc_ok = false;
+      else {
+        Rd v = {c.in.bytes, A.rp_off, A.rp_off + A.rp_len, false};
+        int64_t n_rp = 0, rp_bytes = 0, n_keyed = 0;
+        ok = walk_reset_points(v, stk, [&](int32_t, uint64_t, uint32_t len, bool) {
+          ++n_rp;
+          n_keyed += len != 0;
+          rp_bytes += len;
+        });
+        cnt[6] = n_rp;
+        cnt[kCand] += n_keyed;
+        cnt[kCandBytes] += rp_bytes;
+      }
+    }
+    if (!ok) {
+      malformed = true;
+      note_malformed(c, eb);
+    }
+    if (malformed) st = CRR_LOAD_MALFORMED;
+    else if (!enc_ok) st = CRR_LOAD_NESTED_ENCODING;
+    else if (!vh_ok) st = CRR_LOAD_VERSION_HISTORIES;
+    else if (cnt[6] > CRR_LOAD_MAX_BLOBS) st = CRR_LOAD_TOO_LARGE;   // reset points: interned one against the other
+  }
+  if (st == CRR_LOAD_OK) {   // duplicate IDs within a map (timers: StartedID, or the timer_id the store keys them by)
+    for (uint32_t i = 0; i < n && st == CRR_LOAD_OK; ++i) {
+      const uint32_t k = c.in.blob[b0 + i].kind;
+      if (k == CRR_STATE_EXECUTION) continue;
+      const Rec& a = c.rec()[b0 + i];
+      for (uint32_t j = i + 1; j < n; ++j) {
+        if (c.in.blob[b0 + j].kind != k) continue;
+        const Rec& b = c.rec()[b0 + j];
+        if (a.id == b.id || (k == CRR_STATE_TIMER && a.str_len == b.str_len &&
+                             bytes_equal(c.str(a.str_off), c.str(b.str_off), a.str_len))) {
+          st = CRR_LOAD_DUPLICATE_ID;
+          break;
+        }
+      }
+    }
+  }
+  if (st == CRR_LOAD_OK) {
+    A.current = V.current;
+    cnt[5] = V.n_items;
+    cnt[CRR_LOAD_T_TOKEN] = V.tok_len;
+    R.next_event_id = W.next_event_id;
+    R.n_activity = (int32_t)cnt[0];
+    R.n_timer = (int32_t)cnt[1];
+    R.n_child = (int32_t)cnt[2];
+    R.n_rc = (int32_t)cnt[3];
+    R.n_signal = (int32_t)cnt[4];
+    R.n_vh_items = (int32_t)cnt[5];
+    R.n_reset_points = (int32_t)cnt[6];
+    R.token_src = V.tok_len ? 1 : 0;
+    R.src_next = (int32_t)n;
+    if (P.sticky) fl |= CRR_LOAD_FLAG_STICKY;
+    if (V.n_hist > 1) fl |= CRR_LOAD_FLAG_MULTI_BRANCH;
+  } else {
+    memset(&R, 0, sizeof R);
+    for (int t = 0; t < kCounters; ++t) cnt[t] = 0;
+    note_failed(c);
+  }
+  c.exec()[w] = R;
+  c.aux()[w] = A;
+  c.status()[w] = st;
+  c.flags()[w] = fl;
+  for (int t = 0; t < kCounters; ++t) c.cnt(t)[w] = cnt[t];
+  c.cnt(CRR_LOAD_T_KEYS)[w] = 0;   // emit_wf's
+  c.cnt(CRR_LOAD_T_KEY_BYTES)[w] = 0;
+}
+
+// ---- per workflow: the dense rows ---------------------------------------------------------------------------
+struct Interner {
+  const Ctx& c;
+  uint64_t base;   // the workflow's candidate region: its distinct strings in first-seen order
+  uint32_t n;
+  uint64_t bytes;
+  CRR_HD uint32_t operator()(uint64_t off, uint32_t len) {
+    if (len == 0) return 0;
+    const uint8_t* s = c.str(off);
+    for (uint32_t k = 0; k < n; ++k)
+      if (c.cand_len()[base + k] == len && bytes_equal(c.str(c.cand_off()[base + k]), s, len)) return k + 1;
+    c.cand_off()[base + n] = off;
+    c.cand_len()[base + n] = len;
+    bytes += len;
+    return ++n;
+  }
+};
+
+CRR_HD void emit_wf(const Ctx& c, uint32_t w, Frame* stk) {
+  if (c.status()[w] != CRR_LOAD_OK) return;   // (its counters are zero)
+  const crr_state_wf W = c.in.wf[w];
+  const uint32_t b0 = W.blob_begin, n = W.blob_count;
+  const ExecAux A = c.aux()[w];
+  // (named scalars, not an array indexed by the blob's kind: the offsets stay in registers)
+  const int64_t o0 = c.cnt(0)[w], o1 = c.cnt(1)[w], o2 = c.cnt(2)[w], o3 = c.cnt(3)[w], o4 = c.cnt(4)[w], o5 = c.cnt(5)[w],
+                o6 = c.cnt(6)[w], o7 = c.cnt(CRR_LOAD_T_TOKEN)[w];
+  Interner intern = {c, (uint64_t)c.cnt(kCand)[w], 0, 0};
+  const Rec* recs = c.rec() + b0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t k = c.in.blob[b0 + i].kind;
+    if (k == CRR_STATE_EXECUTION) {
+      crr_reset_point_row* rp = reinterpret_cast<crr_reset_point_row*>(c.rows(6)) + o6;
+      if (A.rp_len) {
+        Rd v = {c.in.bytes, A.rp_off, A.rp_off + A.rp_len, false};
+        walk_reset_points(v, stk, [&](int32_t j, uint64_t off, uint32_t len, bool resettable) {
+          crr_reset_point_row row = {(int32_t)i, j, intern(off, len), CRR_ROW_LIVE | (resettable ? CRR_ROW_RESETTABLE : 0u)};
+          rp[j] = row;
+        });
+      }
+      Rd v = {c.in.bytes, A.vh_off, A.vh_off + A.vh_len, false};
+      VhWalk V;
+      walk_vh(v, A.current, reinterpret_cast<crr_vh_item*>(c.rows(5)) + o5, V, stk);
+      uint8_t* tok = c.tokens() + o7;
+      for (uint32_t q = 0; q < V.tok_len; ++q) tok[q] = c.in.bytes[V.tok_off + q];
+      continue;
+    }
+    const Rec& rc = recs[i];
+    int64_t rank = 0;   // rows ascending by ID: the order the checksum and the replay's finalize use
+    const int64_t my_id = rc.id;
+    for (uint32_t j = 0; j < n; ++j)
+      rank += (c.in.blob[b0 + j].kind == k && recs[j].id < my_id) ? 1 : 0;
+    // the row image goes to its slot as parsed; the fields this pass owns are then set in place
+    if (k == CRR_STATE_ACTIVITY) {
+      crr_activity_row& row = reinterpret_cast<crr_activity_row*>(c.rows(0))[o0 + rank];
+      row = rc.row.act;
+      row.key = intern(rc.str_off, rc.str_len);
+      row.sched_src = (int32_t)i;
+      row.started_src = rc.row.act.started_id == CRR_EMPTY_EVENT_ID ? -1 : (int32_t)i;
+    } else if (k == CRR_STATE_TIMER) {
+      crr_timer_row& row = reinterpret_cast<crr_timer_row*>(c.rows(1))[o1 + rank];
+      row = rc.row.timer;
+      row.key = intern(rc.str_off, rc.str_len);
+      row.src = (int32_t)i;
+    } else if (k == CRR_STATE_CHILD) {
+      crr_child_row& row = reinterpret_cast<crr_child_row*>(c.rows(2))[o2 + rank];
+      row = rc.row.child;
+      row.src = (int32_t)i;
+      row.started_src = rc.row.child.started_id == CRR_EMPTY_EVENT_ID ? -1 : (int32_t)i;
+    } else {
+      crr_initiated_row& row = k == CRR_STATE_REQUEST_CANCEL ? reinterpret_cast<crr_initiated_row*>(c.rows(3))[o3 + rank]
+                                                             : reinterpret_cast<crr_initiated_row*>(c.rows(4))[o4 + rank];
+      row = rc.row.init;
+      row.src = (int32_t)i;
+    }
+  }
+  // Load maps every activity by its ActivityID, a later ScheduleID overwriting an earlier one
+  // (mutable_state_builder.go:311-314; Go ranges over a map there: the header's rule for
+  // CRR_WF_FLAG_RESUME fixes the order -- the greatest ScheduleID wins)
+  crr_activity_row* act = reinterpret_cast<crr_activity_row*>(c.rows(0)) + o0;
+  const int64_t na = c.cnt(0)[w + 1] - o0;
+  for (int64_t i = 0; i < na; ++i) {
+    bool mapped = true;
+    const uint32_t key = act[i].key;
+    for (int64_t j = i + 1; j < na; ++j)
+      if (act[j].key == key) {
+        mapped = false;
+        break;
+      }
+    if (mapped) act[i].flags |= CRR_ROW_MAPPED;
+  }
+  c.cnt(CRR_LOAD_T_KEYS)[w] = intern.n;
+  c.cnt(CRR_LOAD_T_KEY_BYTES)[w] = (int64_t)intern.bytes;
+}
+
+CRR_HD void dict_wf(const Ctx& c, uint32_t w) {
+  const int64_t k0 = c.cnt(CRR_LOAD_T_KEYS)[w], k1 = c.cnt(CRR_LOAD_T_KEYS)[w + 1];
+  uint64_t run = (uint64_t)c.cnt(CRR_LOAD_T_KEY_BYTES)[w];
+  const uint64_t base = (uint64_t)c.cnt(kCand)[w];
+  for (int64_t k = 0; k < k1 - k0; ++k) {
+    const uint32_t len = c.cand_len()[base + k];
+    const uint8_t* s = c.str(c.cand_off()[base + k]);
+    c.key_off()[k0 + k] = run;
+    c.key_len()[k0 + k] = len;
+    uint8_t* d = c.key_bytes() + run;
+    for (uint32_t q = 0; q < len; ++q) d[q] = s[q];
+    run += len;
+  }
+}
+
+inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,
+                         uint64_t failed, uint64_t needed) {
+  memset(S, 0, sizeof *S);
+  S->n_failed = (uint32_t)failed;
+  S->err_blob = err_blob == ~0ull ? -1 : (int64_t)err_blob;
+  for (int t = 0; t < CRR_LOAD_TABLES; ++t) S->totals[t] = (uint64_t)totals[t];
+  S->staging[0] = (uint64_t)totals[kCand];
+  S->staging[1] = (uint64_t)totals[kCandBytes];
+  S->scratch_needed = needed;
+  S->n_blobs = c.in.n_blobs;
+  S->n_wf = c.in.n_wf;
+}
+
+// the layout read / place rebuild from a plan's summary
+inline Layout layout_of(const crr_load_summary& S) {
+  uint64_t tot[kCounters];
+  for (int t = 0; t < CRR_LOAD_TABLES; ++t) tot[t] = S.totals[t];
+  tot[kCand] = S.staging[0];
+  tot[kCandBytes] = S.staging[1];
+  return carve(S.n_blobs, S.n_wf, tot);
+}
+
+}  // namespace crr_load
+#endif  // CADENCE_LOAD_DECODE_H_

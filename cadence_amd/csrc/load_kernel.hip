@@ -1,0 +1,280 @@
+// load_kernel.hip -- persisted mutable-state blobs -> resumable rows on the GPU (include/cadence_load.h).
+//
+// The decoder is load_decode.h (its own bounds-checked thrift reader; shared with the host restatement so
+// the two cannot drift); this file holds the launches:
+//   load_parse_kernel   one lane per blob: a pending entry's struct -> its row image in the scratch
+//   load_count_kernel   one lane per workflow: the execution blob -> the exec row, the nested blobs walked
+//                       to validate and count, duplicate IDs, status / flags, the per-table counts
+//   load_scan_kernel    one block: exclusive prefixes of the counts over workflows (compact_kernel.hip's pattern)
+//   load_emit_kernel    one lane per workflow: rows to their rank by ID, keys interned, MAPPED, items, tokens
+//   load_dict_kernel    one lane per workflow: the key dictionary
+//   load_place_kernel   one lane per device position: the dense rows scattered into a replay's slot tables
+// Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
+// (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
+// A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
+// pending entries, which the states of the replication path keep small (a wavefront-per-workflow variant
+// for large states is not built).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "cadence_ingest.h"
+#include "cadence_load.h"
+#include "load_decode.h"
+#include "stream_device.h"
+
+namespace crr_load {
+namespace {
+
+constexpr int kBlock = 128;
+constexpr int kScanBlock = 1024;
+
+__global__ void __launch_bounds__(kBlock) load_parse_kernel(Ctx c) {
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  const uint32_t b = blockIdx.x * kBlock + threadIdx.x;
+  if (b < c.in.n_blobs) parse_blob(c, b, stk[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kBlock) load_count_kernel(Ctx c) {
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  const uint32_t w = blockIdx.x * kBlock + threadIdx.x;
+  if (w >= c.in.n_wf) return;
+  if (!range_ok(c, w)) c.err()[2 + kCounters] = 1;   // (every writer stores the same value)
+  count_wf(c, w, stk[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kBlock) load_emit_kernel(Ctx c) {
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  const uint32_t w = blockIdx.x * kBlock + threadIdx.x;
+  if (w < c.in.n_wf) emit_wf(c, w, stk[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kBlock) load_dict_kernel(Ctx c) {
+  const uint32_t w = blockIdx.x * kBlock + threadIdx.x;
+  if (w < c.in.n_wf) dict_wf(c, w);
+}
+
+// one block: counters [first, last) scanned in place over the n_wf workflows (each thread a contiguous chunk,
+// Hillis-Steele over the 1024 chunk sums); the totals also go to totals[t] for the host to read in one copy
+__global__ void __launch_bounds__(kScanBlock) load_scan_kernel(Ctx c, uint32_t mask, uint64_t* totals) {
+  __shared__ int64_t part[kScanBlock];
+  const uint32_t n = c.in.n_wf;
+  const uint32_t per = (n + kScanBlock - 1) / kScanBlock;
+  for (int t = 0; t < kCounters; ++t) {
+    if (!((mask >> t) & 1u)) continue;
+    int64_t* p = c.cnt(t);
+    const uint32_t lo = min((uint64_t)threadIdx.x * per, (uint64_t)n), hi = min((uint64_t)lo + per, (uint64_t)n);
+    int64_t s = 0;
+    for (uint32_t i = lo; i < hi; ++i) s += p[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < kScanBlock; d <<= 1) {
+      const int64_t o = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
+      __syncthreads();
+      part[threadIdx.x] += o;
+      __syncthreads();
+    }
+    int64_t run = part[threadIdx.x] - s;
+    for (uint32_t i = lo; i < hi; ++i) {
+      const int64_t x = p[i];
+      p[i] = run;
+      run += x;
+    }
+    if (threadIdx.x == kScanBlock - 1) {
+      p[n] = part[kScanBlock - 1];
+      totals[t] = (uint64_t)part[kScanBlock - 1];
+    }
+    __syncthreads();
+  }
+}
+
+struct PlaceArgs {
+  const crr_workflow* wf;
+  const uint32_t* perm;
+  uint32_t n_pos, stride, wave_begin, n_loaded;
+  crr_outputs out;
+};
+
+__global__ void __launch_bounds__(kBlock) load_place_kernel(Ctx c, PlaceArgs a) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= a.n_pos) return;
+  const crr_workflow& D = a.wf[p];
+  if (!(D.flags & CRR_WF_FLAG_RESUME)) return;
+  const uint32_t w = a.perm ? a.perm[p] : p;
+  if (w >= a.n_loaded || c.status()[w] != CRR_LOAD_OK) return;
+  const int64_t st = p >= a.wave_begin ? 1 : (int64_t)a.stride;
+  const crr_exec_row& R = c.exec()[w];
+  crr_exec_row& X = a.out.exec[p];
+  // each table by name (no arrays indexed by table: everything stays in registers)
+  auto count = [&](int t) { return c.cnt(t)[w + 1] - c.cnt(t)[w]; };
+  auto fits1 = [&](int t, int32_t cap, const void* dst) {
+    const int64_t n = count(t);
+    return n <= (int64_t)(cap < 0 ? 0 : cap) && (n == 0 || dst != nullptr);
+  };
+  const bool fits = fits1(0, D.act_cap, a.out.act) && fits1(1, D.timer_cap, a.out.timer) && fits1(2, D.child_cap, a.out.child) &&
+                    fits1(3, D.rc_cap, a.out.rc) && fits1(4, D.sig_cap, a.out.sig) && fits1(5, D.vh_cap, a.out.vh) &&
+                    fits1(6, D.rp_cap, a.out.rp);
+  if (!fits) {   // sized too small by the host: nothing of it written but the exec row's verdict
+    X = R;
+    X.status = CRR_ERR_CAPACITY;
+    X.fail_step = R.src_next;
+    X.n_activity = X.n_timer = X.n_child = X.n_rc = X.n_signal = X.n_vh_items = X.n_reset_points = 0;
+    return;
+  }
+  X = R;
+  auto put = [&](int t, int64_t base, void* dst, int64_t* ids) {
+    const uint32_t words = kRowBytes[t] / 8;   // every row type is a multiple of 8 bytes
+    const int64_t off = c.cnt(t)[w], n = count(t);
+    const uint64_t* s = reinterpret_cast<const uint64_t*>(c.rows(t) + (uint64_t)off * kRowBytes[t]);
+    for (int64_t j = 0; j < n; ++j) {
+      uint64_t* q = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(dst) + (uint64_t)(base + j * st) * kRowBytes[t]);
+      for (uint32_t k = 0; k < words; ++k) q[k] = s[(uint64_t)j * words + k];
+      // the live-ID sidecar: each pending map's ID is its row's first field
+      if (ids) ids[base + j * st] = (int64_t)s[(uint64_t)j * words];
+    }
+  };
+  put(0, D.act_base, a.out.act, a.out.live_ids[0]);
+  put(1, D.timer_base, a.out.timer, a.out.live_ids[1]);
+  put(2, D.child_base, a.out.child, a.out.live_ids[2]);
+  put(3, D.rc_base, a.out.rc, a.out.live_ids[3]);
+  put(4, D.sig_base, a.out.sig, a.out.live_ids[4]);
+  put(5, D.vh_base, a.out.vh, nullptr);
+  put(6, D.rp_base, a.out.rp, nullptr);
+}
+
+inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
+
+constexpr uint32_t kScanA = 0xFFFu & ~((1u << CRR_LOAD_T_KEYS) | (1u << CRR_LOAD_T_KEY_BYTES));
+constexpr uint32_t kScanB = (1u << CRR_LOAD_T_KEYS) | (1u << CRR_LOAD_T_KEY_BYTES);
+
+}  // namespace
+}  // namespace crr_load
+
+extern "C" {
+
+using namespace crr_load;
+
+size_t crr_load_scratch_bytes(uint32_t n_blobs, uint32_t n_wf) {
+  uint64_t tot[kCounters] = {0};
+  tot[0] = n_blobs;   // the widest row type for every pending entry
+  tot[5] = tot[6] = 8ull * n_wf;
+  tot[CRR_LOAD_T_TOKEN] = 128ull * n_wf;
+  tot[kCand] = (uint64_t)n_blobs + 8ull * n_wf;
+  tot[kCandBytes] = 32ull * tot[kCand];
+  return (size_t)carve(n_blobs, n_wf, tot).end;
+}
+
+int crr_load_states_plan(const crr_state_batch* in, void* scratch, size_t scratch_bytes, crr_load_summary* summary,
+                         void* stream) {
+  if (!in || !summary || !scratch || ((uintptr_t)scratch & 15u)) return -1;
+  if (in->n_blobs && (!in->bytes || !in->blob_off || !in->blob)) return -1;
+  if (in->n_wf && !in->wf) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  Ctx c;
+  c.in = *in;
+  c.s = static_cast<uint8_t*>(scratch);
+  c.L = carve(in->n_blobs, in->n_wf, nullptr);
+  memset(summary, 0, sizeof *summary);
+  summary->err_blob = -1;
+  summary->n_blobs = in->n_blobs;
+  summary->n_wf = in->n_wf;
+  if (c.L.end > scratch_bytes) {
+    summary->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    summary->scratch_needed = crr_load_scratch_bytes(in->n_blobs, in->n_wf);
+    return 0;
+  }
+  if (in->n_wf == 0) return 0;
+  hipError_t e;
+  // err()[0] = no malformed blob, [1] = failed workflows, [2..] = the scans' totals, then the bad-ranges mark
+  if ((e = hipMemsetAsync(c.err(), 0xFF, sizeof(uint64_t), s)) != hipSuccess) return (int)e;
+  if ((e = hipMemsetAsync(c.err() + 1, 0, (2 + kCounters) * sizeof(uint64_t), s)) != hipSuccess) return (int)e;
+  uint64_t* d_tot = c.err() + 2;
+  if (in->n_blobs) hipLaunchKernelGGL(load_parse_kernel, grid_of(in->n_blobs), dim3(kBlock), 0, s, c);
+  hipLaunchKernelGGL(load_count_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c);
+  hipLaunchKernelGGL(load_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, c, kScanA, d_tot);
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[3 + kCounters];
+  if ((e = hipMemcpyAsync(h, c.err(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if (h[2 + kCounters]) return -1;   // blob ranges not consecutive or not covering the blobs
+  c.L = carve(in->n_blobs, in->n_wf, h + 2);
+  if (c.L.end > scratch_bytes) {
+    summary->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    summary->scratch_needed = c.L.end;
+    return 0;
+  }
+  hipLaunchKernelGGL(load_emit_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c);
+  hipLaunchKernelGGL(load_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, c, kScanB, d_tot);
+  hipLaunchKernelGGL(load_dict_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c);
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  if ((e = hipMemcpyAsync(h, c.err(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  int64_t totals[kCounters];
+  for (int t = 0; t < kCounters; ++t) totals[t] = (int64_t)h[2 + t];
+  fill_summary(summary, c, totals, h[0], h[1], c.L.end);
+  return 0;
+}
+
+static bool plan_usable(const void* scratch, size_t scratch_bytes, const crr_load_summary* S, Ctx& c) {
+  if (!scratch || !S || S->err != 0 || ((uintptr_t)scratch & 15u)) return false;
+  c.s = const_cast<uint8_t*>(static_cast<const uint8_t*>(scratch));
+  c.L = layout_of(*S);
+  memset(&c.in, 0, sizeof c.in);
+  c.in.n_blobs = S->n_blobs;
+  c.in.n_wf = S->n_wf;
+  return c.L.end <= scratch_bytes && c.L.end == S->scratch_needed;
+}
+
+int crr_load_states_read(const void* scratch, size_t scratch_bytes, const crr_load_summary* summary_host,
+                         const crr_load_image* dst, void* stream) {
+  Ctx c;
+  if (!dst || !plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  const crr_load_summary& S = *summary_host;
+  const size_t n = S.n_wf;
+  if (n == 0) return 0;
+  hipError_t e = hipSuccess;
+  auto copy = [&](void* d, const void* src, size_t bytes) {
+    if (d && bytes && e == hipSuccess) e = hipMemcpyAsync(d, src, bytes, hipMemcpyDefault, s);
+  };
+  copy(dst->exec, c.exec(), n * sizeof(crr_exec_row));
+  for (int t = 0; t < 7; ++t) copy(dst->rows[t], c.rows(t), (size_t)S.totals[t] * kRowBytes[t]);
+  copy(dst->offsets, c.cnt(0), (size_t)CRR_LOAD_TABLES * (n + 1) * sizeof(int64_t));
+  copy(dst->tokens, c.tokens(), (size_t)S.totals[CRR_LOAD_T_TOKEN]);
+  copy(dst->key_off, c.key_off(), (size_t)S.totals[CRR_LOAD_T_KEYS] * sizeof(uint64_t));
+  copy(dst->key_len, c.key_len(), (size_t)S.totals[CRR_LOAD_T_KEYS] * sizeof(uint32_t));
+  copy(dst->key_bytes, c.key_bytes(), (size_t)S.totals[CRR_LOAD_T_KEY_BYTES]);
+  copy(dst->status, c.status(), n * sizeof(int32_t));
+  copy(dst->flags, c.flags(), n * sizeof(uint32_t));
+  return (int)e;
+}
+
+int crr_load_states_place(const void* scratch, size_t scratch_bytes, const crr_load_summary* summary_host,
+                          const crr_inputs* layout, const uint32_t* perm, const crr_outputs* out, void* stream) {
+  Ctx c;
+  if (!layout || !out || !out->exec || !plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
+  if (layout->n_wf && !layout->wf) return -1;
+  if (layout->stride == 0 || ((layout->flags & CRR_IN_WAVE_TAIL) && layout->wave_begin > layout->n_wf)) return -1;
+  int ids = 0;
+  for (int t = 0; t < 5; ++t) ids += out->live_ids[t] != nullptr;
+  if (ids != 0 && ids != 5) return -1;   // all five set or none
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (layout->n_wf == 0 || summary_host->n_wf == 0) return 0;
+  PlaceArgs a;
+  a.wf = layout->wf;
+  a.perm = perm;
+  a.n_pos = layout->n_wf;
+  a.stride = layout->stride;
+  a.wave_begin = (layout->flags & CRR_IN_WAVE_TAIL) ? layout->wave_begin : layout->n_wf;
+  a.n_loaded = summary_host->n_wf;
+  a.out = *out;
+  hipLaunchKernelGGL(load_place_kernel, grid_of(a.n_pos), dim3(kBlock), 0, s, c, a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1,0 +1,105 @@
+// load_states.cpp -- crr_load_states_host: the host restatement of the persisted mutable-state loader
+// (include/cadence_load.h).  The decoder itself is load_decode.h, the same text the gfx950 kernels of
+// load_kernel.hip compile; this file runs its phases as loops (optionally over threads), with serial
+// prefix scans between them, over a scratch laid out exactly like the device's.
+#include <stdlib.h>
+
+#include <thread>
+#include <vector>
+
+#include "load_decode.h"
+
+namespace {
+
+using namespace crr_load;
+
+template <class Fn>
+void parallel_for(uint32_t n, int threads, Fn fn) {
+  if (threads <= 1 || n < 1024) {
+    Frame stk[kMaxDepth];
+    for (uint32_t i = 0; i < n; ++i) fn(i, stk);
+    return;
+  }
+  std::vector<std::thread> pool;
+  const uint32_t per = (n + threads - 1) / threads;
+  for (int t = 0; t < threads; ++t) {
+    const uint32_t lo = (uint32_t)t * per, hi = lo + per < n ? lo + per : n;
+    if (lo >= hi) break;
+    pool.emplace_back([=] {
+      Frame stk[kMaxDepth];
+      for (uint32_t i = lo; i < hi; ++i) fn(i, stk);
+    });
+  }
+  for (auto& th : pool) th.join();
+}
+
+void scan(const Ctx& c, int t) {
+  int64_t* p = c.cnt(t);
+  int64_t run = 0;
+  for (uint32_t w = 0; w < c.in.n_wf; ++w) {
+    const int64_t x = p[w];
+    p[w] = run;
+    run += x;
+  }
+  p[c.in.n_wf] = run;
+}
+
+}  // namespace
+
+extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_image* dst, crr_load_summary* summary,
+                                    int threads) {
+  if (!in || !summary) return -1;
+  if (in->n_blobs && (!in->bytes || !in->blob_off || !in->blob)) return -1;
+  if (in->n_wf && !in->wf) return -1;
+  const uint32_t n_wf = in->n_wf;
+  uint64_t blobs = 0;
+  for (uint32_t w = 0; w < n_wf; ++w) {   // consecutive ranges covering the blobs
+    if (in->wf[w].blob_begin != blobs) return -1;
+    blobs += in->wf[w].blob_count;
+  }
+  if (blobs != in->n_blobs) return -1;
+  Ctx c;
+  c.in = *in;
+  c.L = carve(in->n_blobs, n_wf, nullptr);
+  uint8_t* fixed = static_cast<uint8_t*>(calloc(c.L.end + 16, 1));
+  if (!fixed) return -2;
+  c.s = fixed;
+  c.err()[0] = ~0ull;
+  parallel_for(in->n_blobs, threads, [&](uint32_t b, Frame* stk) { parse_blob(c, b, stk); });
+  parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { count_wf(c, w, stk); });
+  for (int t = 0; t < kCounters; ++t)
+    if (t != CRR_LOAD_T_KEYS && t != CRR_LOAD_T_KEY_BYTES) scan(c, t);
+  uint64_t tot[kCounters];
+  for (int t = 0; t < kCounters; ++t) tot[t] = (uint64_t)c.cnt(t)[n_wf];
+  const Layout full = carve(in->n_blobs, n_wf, tot);
+  uint8_t* s = static_cast<uint8_t*>(realloc(fixed, full.end + 16));
+  if (!s) {
+    free(fixed);
+    return -2;
+  }
+  memset(s + c.L.end, 0, full.end + 16 - c.L.end);
+  c.s = s;
+  c.L = full;
+  parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { emit_wf(c, w, stk); });
+  scan(c, CRR_LOAD_T_KEYS);
+  scan(c, CRR_LOAD_T_KEY_BYTES);
+  parallel_for(n_wf, threads, [&](uint32_t w, Frame*) { dict_wf(c, w); });
+  int64_t totals[kCounters];
+  for (int t = 0; t < kCounters; ++t) totals[t] = c.cnt(t)[n_wf];
+  fill_summary(summary, c, totals, c.err()[0], c.err()[1], full.end);
+  if (dst) {
+    const size_t n = n_wf;
+    if (dst->exec) memcpy(dst->exec, c.exec(), n * sizeof(crr_exec_row));
+    for (int t = 0; t < 7; ++t)
+      if (dst->rows[t]) memcpy(dst->rows[t], c.rows(t), (size_t)totals[t] * kRowBytes[t]);
+    if (dst->offsets) memcpy(dst->offsets, c.cnt(0), (size_t)CRR_LOAD_TABLES * (n + 1) * sizeof(int64_t));
+    if (dst->tokens) memcpy(dst->tokens, c.tokens(), (size_t)totals[CRR_LOAD_T_TOKEN]);
+    if (dst->key_off) memcpy(dst->key_off, c.key_off(), (size_t)totals[CRR_LOAD_T_KEYS] * sizeof(uint64_t));
+    if (dst->key_len) memcpy(dst->key_len, c.key_len(), (size_t)totals[CRR_LOAD_T_KEYS] * sizeof(uint32_t));
+    if (dst->key_bytes) memcpy(dst->key_bytes, c.key_bytes(), (size_t)totals[CRR_LOAD_T_KEY_BYTES]);
+    if (dst->status) memcpy(dst->status, c.status(), n * sizeof(int32_t));
+    if (dst->flags) memcpy(dst->flags, c.flags(), n * sizeof(uint32_t));
+  }
+  free(s);
+  return 0;
+}

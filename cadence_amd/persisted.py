@@ -1,0 +1,554 @@
+"""Persisted mutable states: the SQL store's state blobs <-> the engine's resumable rows.
+
+``encode_states`` is the writer side -- what ``GetWorkflowExecution`` returns for a replayed state: one
+``sqlblobs.WorkflowExecutionInfo`` blob per execution and one ``ActivityInfo`` / ``TimerInfo`` /
+``ChildExecutionInfo`` / ``RequestCancelInfo`` / ``SignalInfo`` blob per pending entry, in plain thrift
+binary (``common/persistence/serialization/thrift_decoder.go:161-165``: no preamble), with the key columns
+stored beside each blob (``common/persistence/sql/workflowStateMaps.go``).  Every field the Go writer sets
+(``serialization/thrift_mapper.go:185-512``) is written, so the loader's skipping is exercised on realistic
+blobs; it is the reference encoder for a cgo shim's tests.
+
+``load_states_host`` decodes such a batch with the host restatement (``crr_load_states_host``) and
+``StateLoader`` with the device implementation (``crr_load_states_plan`` / ``_read`` / ``_place``,
+``include/cadence_load.h``).  Both return the dense loaded image as a ``LoadedImage`` (a
+``flatten.LoadedStates`` plus tokens, dictionaries, statuses and flags).
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+import random
+import struct
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+
+from . import abi
+from .flatten import HistoryBatch, LoadedStates
+from .history import WorkflowHistory, det_uuid, thrift_history_branch_token
+from .result import ReplayResult
+from .thrift_codec import T_BOOL, T_DOUBLE, T_I32, T_I64, T_LIST, T_MAP, T_STRING, T_STRUCT, W
+
+
+def _table(spec: str):
+    return [(n, int(i), t) for n, i, t in (x.split(":") for x in spec.split())]
+
+
+# .gen/go/sqlblobs/sqlblobs.go: (field, id, thrift type) of the six state structs
+FIELDS = {
+    "WorkflowExecutionInfo": _table(
+        "ParentDomainID:10:binary ParentWorkflowID:12:binary ParentRunID:14:binary InitiatedID:16:i64 "
+        "CompletionEventBatchID:18:i64 CompletionEvent:20:binary CompletionEventEncoding:22:binary TaskList:24:binary "
+        "WorkflowTypeName:26:binary WorkflowTimeoutSeconds:28:i32 DecisionTaskTimeoutSeconds:30:i32 "
+        "ExecutionContext:32:binary State:34:i32 CloseStatus:36:i32 StartVersion:38:i64 LastWriteEventID:44:i64 "
+        "LastEventTaskID:48:i64 LastFirstEventID:50:i64 LastProcessedEvent:52:i64 StartTimeNanos:54:i64 "
+        "LastUpdatedTimeNanos:56:i64 DecisionVersion:58:i64 DecisionScheduleID:60:i64 DecisionStartedID:62:i64 "
+        "DecisionTimeout:64:i32 DecisionAttempt:66:i64 DecisionStartedTimestampNanos:68:i64 "
+        "DecisionScheduledTimestampNanos:69:i64 CancelRequested:70:bool DecisionOriginalScheduledTimestampNanos:71:i64 "
+        "CreateRequestID:72:binary DecisionRequestID:74:binary CancelRequestID:76:binary StickyTaskList:78:binary "
+        "StickyScheduleToStartTimeout:80:i64 RetryAttempt:82:i64 RetryInitialIntervalSeconds:84:i32 "
+        "RetryMaximumIntervalSeconds:86:i32 RetryMaximumAttempts:88:i32 RetryExpirationSeconds:90:i32 "
+        "RetryBackoffCoefficient:92:double RetryExpirationTimeNanos:94:i64 RetryNonRetryableErrors:96:list "
+        "HasRetryPolicy:98:bool CronSchedule:100:binary EventStoreVersion:102:i32 EventBranchToken:104:binary "
+        "SignalCount:106:i64 HistorySize:108:i64 ClientLibraryVersion:110:binary ClientFeatureVersion:112:binary "
+        "ClientImpl:114:binary AutoResetPoints:115:binary AutoResetPointsEncoding:116:binary SearchAttributes:118:map "
+        "Memo:120:map VersionHistories:122:binary VersionHistoriesEncoding:124:binary"),
+    "ActivityInfo": _table(
+        "Version:10:i64 ScheduledEventBatchID:12:i64 ScheduledEvent:14:binary ScheduledEventEncoding:16:binary "
+        "ScheduledTimeNanos:18:i64 StartedID:20:i64 StartedEvent:22:binary StartedEventEncoding:24:binary "
+        "StartedTimeNanos:26:i64 ActivityID:28:binary RequestID:30:binary ScheduleToStartTimeoutSeconds:32:i32 "
+        "ScheduleToCloseTimeoutSeconds:34:i32 StartToCloseTimeoutSeconds:36:i32 HeartbeatTimeoutSeconds:38:i32 "
+        "CancelRequested:40:bool CancelRequestID:42:i64 TimerTaskStatus:44:i32 Attempt:46:i32 TaskList:48:binary "
+        "StartedIdentity:50:binary HasRetryPolicy:52:bool RetryInitialIntervalSeconds:54:i32 "
+        "RetryMaximumIntervalSeconds:56:i32 RetryMaximumAttempts:58:i32 RetryExpirationTimeNanos:60:i64 "
+        "RetryBackoffCoefficient:62:double RetryNonRetryableErrors:64:list RetryLastFailureReason:66:binary "
+        "RetryLastWorkerIdentity:68:binary RetryLastFailureDetails:70:binary"),
+    "TimerInfo": _table("Version:10:i64 StartedID:12:i64 ExpiryTimeNanos:14:i64 TaskID:16:i64"),
+    "ChildExecutionInfo": _table(
+        "Version:10:i64 InitiatedEventBatchID:12:i64 StartedID:14:i64 InitiatedEvent:16:binary "
+        "InitiatedEventEncoding:18:binary StartedWorkflowID:20:binary StartedRunID:22:binary StartedEvent:24:binary "
+        "StartedEventEncoding:26:binary CreateRequestID:28:binary DomainID:29:binary DomainName:30:binary "
+        "WorkflowTypeName:32:binary ParentClosePolicy:35:i32"),
+    "RequestCancelInfo": _table("Version:10:i64 InitiatedEventBatchID:11:i64 CancelRequestID:12:binary"),
+    "SignalInfo": _table("Version:10:i64 InitiatedEventBatchID:11:i64 RequestID:12:binary Name:14:binary Input:16:binary "
+                         "Control:18:binary"),
+}
+KIND_STRUCT = ["WorkflowExecutionInfo", "ActivityInfo", "TimerInfo", "ChildExecutionInfo", "RequestCancelInfo",
+               "SignalInfo"]
+THRIFT_TYPE = {"bool": T_BOOL, "double": T_DOUBLE, "i32": T_I32, "i64": T_I64, "binary": T_STRING, "list": T_LIST,
+               "map": T_MAP, "struct": T_STRUCT}
+
+
+def write_value(w: W, fid: int, typ: str, v):
+    """One field of thrift type ``typ`` (list: list<string>; map: map<string, binary>)."""
+    if typ == "i64":
+        w.i64(fid, v)
+    elif typ == "i32":
+        w.i32(fid, v)
+    elif typ == "bool":
+        w.boolean(fid, v)
+    elif typ == "double":
+        w.double(fid, v)
+    elif typ == "binary":
+        w.string(fid, v)
+    elif typ == "list":
+        w.list_strings(fid, list(v))
+    elif typ == "map":
+        w.map_string_binary(fid, dict(v))
+    else:
+        raise ValueError(typ)
+
+
+def encode_struct(name: str, values: Dict[str, object], fields=None) -> bytes:
+    """thriftrw's struct encoding: the set (non-None) fields in ascending id, then the stop byte."""
+    w = W()
+    for fname, fid, typ in sorted(fields or FIELDS[name], key=lambda f: f[1]):
+        v = values.get(fname)
+        if v is not None:
+            write_value(w, fid, typ, v)
+    unknown = set(values) - {f[0] for f in (fields or FIELDS[name])}
+    if unknown:
+        raise KeyError(f"{name}: no field {sorted(unknown)}")
+    w.b += b"\x00"
+    return bytes(w.b)
+
+
+def to_unix_nano(t: int) -> int:
+    """timeToUnixNanoPtr: the Go zero time (rows: ZERO_TIME) is written as time.Time{}.UnixNano()."""
+    return abi.GO_ZERO_TIME_NANOS if int(t) == abi.ZERO_TIME else int(t)
+
+
+def encode_version_histories(current: int, histories: Sequence) -> bytes:
+    """shared.VersionHistories as a thriftrw DataBlob: ``histories`` = [(branch token, [(event id, version)])]."""
+    w = W()
+    w.b += b"\x59"
+    w.i32(10, current)
+    w.field(T_LIST, 20)
+    w.b += bytes([T_STRUCT]) + struct.pack(">i", len(histories))
+    for token, items in histories:
+        w.string(10, token)
+        w.field(T_LIST, 20)
+        w.b += bytes([T_STRUCT]) + struct.pack(">i", len(items))
+        for eid, ver in items:
+            w.i64(10, eid)
+            w.i64(20, ver)
+            w.b += b"\x00"
+        w.b += b"\x00"
+    w.b += b"\x00"
+    return bytes(w.b)
+
+
+def encode_reset_points(points: Sequence) -> bytes:
+    """shared.ResetPoints as a thriftrw DataBlob (the layout thrift_codec._reset_points writes inside a start
+    event): ``points`` = [(binary checksum, resettable)]."""
+    w = W()
+    w.b += b"\x59"
+    w.field(T_LIST, 10)
+    w.b += bytes([T_STRUCT]) + struct.pack(">i", len(points))
+    for i, (bc, resettable) in enumerate(points):
+        w.string(10, bc)
+        w.string(20, f"run-{i}")
+        w.i64(30, 4 + i)
+        w.i64(40, 1_500_000_000_000_000_000 + i)
+        w.i64(50, 0)
+        w.boolean(60, resettable)
+        w.b += b"\x00"
+    w.b += b"\x00"
+    return bytes(w.b)
+
+
+@dataclasses.dataclass
+class StateBlobSet:
+    """Host image of ``crr_state_batch``."""
+    bytes: np.ndarray        # uint8: the blobs, then abi.INGEST_PAD zero bytes
+    blob_off: np.ndarray     # uint64 [n_blobs + 1]
+    blob: np.ndarray         # abi.STATE_BLOB [n_blobs]
+    wf: np.ndarray           # abi.STATE_WF [n_wf]
+    strings: np.ndarray      # uint8
+
+    @property
+    def n_blobs(self) -> int:
+        return int(self.blob.shape[0])
+
+    @property
+    def n_wf(self) -> int:
+        return int(self.wf.shape[0])
+
+    @property
+    def n_bytes(self) -> int:
+        return int(self.blob_off[-1])
+
+    def blob_bytes(self, b: int) -> bytes:
+        return self.bytes[int(self.blob_off[b]):int(self.blob_off[b + 1])].tobytes()
+
+
+def build_blob_set(workflows: Sequence) -> StateBlobSet:
+    """``workflows``: per execution ``(next_event_id, [(kind, id, aux_time, timer_id, blob bytes), ...])``."""
+    data = bytearray()
+    strings = bytearray()
+    offs = [0]
+    blob_rows, wf_rows = [], []
+    for nei, blobs in workflows:
+        wf_rows.append((len(blob_rows), len(blobs), nei))
+        for kind, bid, aux, timer_id, raw in blobs:
+            s = timer_id.encode() if isinstance(timer_id, str) else bytes(timer_id or b"")
+            blob_rows.append((kind, len(s), bid, aux, len(strings)))
+            strings += s
+            data += raw
+            offs.append(len(data))
+    return StateBlobSet(
+        bytes=np.frombuffer(bytes(data) + bytes(abi.INGEST_PAD), np.uint8).copy(),
+        blob_off=np.array(offs, np.uint64),
+        blob=np.array(blob_rows, dtype=abi.STATE_BLOB) if blob_rows else np.zeros(0, abi.STATE_BLOB),
+        wf=np.array(wf_rows, dtype=abi.STATE_WF) if wf_rows else np.zeros(0, abi.STATE_WF),
+        strings=np.frombuffer(bytes(strings) + b"\0", np.uint8).copy())
+
+
+def _inverse(interner: Optional[Dict[str, int]]) -> Dict[int, str]:
+    return {v: k for k, v in (interner or {"": 0}).items()}
+
+
+def execution_values(ex, token: bytes, vh_items, points, sticky: str = "", decoy_branch: bool = False) -> Dict[str, object]:
+    """Field values of the execution blob for exec row ``ex`` (workflowExecutionInfoToThrift: every pointer
+    field set; the nil-able ones the replay path leaves nil are omitted)."""
+    src = int(ex["decision_request_src"])
+    request_id = "emptyUuid" if src == abi.SRC_EMPTY_UUID else ("" if src == abi.SRC_NONE else det_uuid("decision", src))
+    histories = [(token, vh_items)]
+    current = 0
+    if decoy_branch:   # a second, non-current branch in front of the current one
+        histories = [(b"decoy-branch-token", [(1, 0), (7, 3)])] + histories
+        current = 1
+    v = {
+        "ParentWorkflowID": "", "InitiatedID": abi.EMPTY_EVENT_ID, "CompletionEventEncoding": "",
+        "TaskList": "task-list", "WorkflowTypeName": "workflow-type", "WorkflowTimeoutSeconds": 3600,
+        "DecisionTaskTimeoutSeconds": int(ex["decision_start_to_close"]), "ExecutionContext": b"ctx",
+        "State": int(ex["state"]), "CloseStatus": int(ex["close_status"]), "StartVersion": 0,
+        "LastEventTaskID": int(ex["last_event_task_id"]), "LastFirstEventID": int(ex["last_first_event_id"]),
+        "LastProcessedEvent": int(ex["last_processed_event"]), "StartTimeNanos": 1_600_000_000_000_000_000,
+        "LastUpdatedTimeNanos": 1_600_000_000_500_000_000, "DecisionVersion": int(ex["decision_version"]),
+        "DecisionScheduleID": int(ex["decision_schedule_id"]), "DecisionStartedID": int(ex["decision_started_id"]),
+        "DecisionTimeout": int(ex["decision_timeout"]), "DecisionAttempt": int(ex["decision_attempt"]),
+        "DecisionStartedTimestampNanos": to_unix_nano(ex["decision_started_ts"]),
+        "DecisionScheduledTimestampNanos": to_unix_nano(ex["decision_scheduled_ts"]),
+        "CancelRequested": bool(int(ex["flags"]) & abi.EXEC_CANCEL_REQUESTED),
+        "DecisionOriginalScheduledTimestampNanos": to_unix_nano(ex["decision_orig_scheduled_ts"]),
+        "CreateRequestID": det_uuid("create"), "DecisionRequestID": request_id, "CancelRequestID": "",
+        "StickyTaskList": sticky, "StickyScheduleToStartTimeout": 0, "RetryAttempt": 0,
+        "RetryInitialIntervalSeconds": 1, "RetryMaximumIntervalSeconds": 100, "RetryMaximumAttempts": 5,
+        "RetryExpirationSeconds": 0, "RetryBackoffCoefficient": 2.0,
+        # ExpirationTime: an unset one is the Go zero time
+        "RetryExpirationTimeNanos": int(ex["expiration_ns"]) or abi.GO_ZERO_TIME_NANOS,
+        "RetryNonRetryableErrors": ["bad-input"], "HasRetryPolicy": bool(int(ex["expiration_ns"])),
+        "CronSchedule": "", "EventStoreVersion": 2, "EventBranchToken": token, "SignalCount": int(ex["signal_count"]),
+        "HistorySize": 4096, "ClientLibraryVersion": "1.7.0", "ClientFeatureVersion": "1.7.0", "ClientImpl": "uber-go",
+        "AutoResetPoints": encode_reset_points(points), "AutoResetPointsEncoding": "thriftrw",
+        "SearchAttributes": {"CustomKeywordField": b'"v"'}, "Memo": {"note": b"memo"},
+        "VersionHistories": encode_version_histories(current, histories), "VersionHistoriesEncoding": "thriftrw",
+    }
+    if int(ex["completion_event_batch_id"]) != abi.EMPTY_EVENT_ID:   # a *int64: nil until the workflow closes
+        v["CompletionEventBatchID"] = int(ex["completion_event_batch_id"])
+    return v
+
+
+def activity_values(r, activity_id: str) -> Dict[str, object]:
+    return {
+        "Version": int(r["version"]), "ScheduledEventBatchID": int(r["scheduled_batch_id"]),
+        "ScheduledEvent": b"scheduled-event", "ScheduledEventEncoding": "thriftrw",
+        "ScheduledTimeNanos": to_unix_nano(r["scheduled_time"]), "StartedID": int(r["started_id"]),
+        "StartedEventEncoding": "", "StartedTimeNanos": to_unix_nano(r["started_time"]), "ActivityID": activity_id,
+        "RequestID": "" if int(r["started_id"]) == abi.EMPTY_EVENT_ID else det_uuid("activity", int(r["schedule_id"])),
+        "ScheduleToStartTimeoutSeconds": int(r["schedule_to_start"]),
+        "ScheduleToCloseTimeoutSeconds": int(r["schedule_to_close"]),
+        "StartToCloseTimeoutSeconds": int(r["start_to_close"]), "HeartbeatTimeoutSeconds": int(r["heartbeat"]),
+        "CancelRequested": bool(int(r["flags"]) & abi.ROW_CANCEL_REQUESTED), "CancelRequestID": int(r["cancel_request_id"]),
+        "TimerTaskStatus": int(r["timer_task_status"]), "Attempt": int(r["attempt"]), "TaskList": "activity-tl",
+        "StartedIdentity": "worker", "HasRetryPolicy": bool(int(r["flags"]) & abi.ROW_HAS_RETRY),
+        "RetryInitialIntervalSeconds": 1, "RetryMaximumIntervalSeconds": 100, "RetryMaximumAttempts": 5,
+        "RetryExpirationTimeNanos": abi.GO_ZERO_TIME_NANOS, "RetryBackoffCoefficient": 2.0,
+        "RetryNonRetryableErrors": ["bad-input"], "RetryLastFailureReason": "", "RetryLastWorkerIdentity": "",
+    }
+
+
+def timer_values(r) -> Dict[str, object]:
+    return {"Version": int(r["version"]), "StartedID": int(r["started_id"]),
+            "ExpiryTimeNanos": to_unix_nano(r["expiry_time"]), "TaskID": int(r["task_status"])}
+
+
+def child_values(r) -> Dict[str, object]:
+    started = int(r["started_id"]) != abi.EMPTY_EVENT_ID
+    return {"Version": int(r["version"]), "InitiatedEventBatchID": int(r["initiated_batch_id"]),
+            "StartedID": int(r["started_id"]), "InitiatedEvent": b"initiated-event", "InitiatedEventEncoding": "thriftrw",
+            "StartedWorkflowID": "child-wf" if started else "", "StartedRunID": b"0123456789abcdef" if started else None,
+            "StartedEventEncoding": "", "CreateRequestID": det_uuid("child", int(r["initiated_id"])),
+            "DomainID": "domain-id", "DomainName": "domain-a", "WorkflowTypeName": "child-type", "ParentClosePolicy": 0}
+
+
+def initiated_values(r, signal: bool) -> Dict[str, object]:
+    v = {"Version": int(r["version"]), "InitiatedEventBatchID": int(r["initiated_batch_id"])}
+    if signal:
+        v.update(RequestID=det_uuid("signal", int(r["initiated_id"])), Name="sig", Input=b"signal-input", Control=b"c")
+    else:
+        v["CancelRequestID"] = det_uuid("cancel", int(r["initiated_id"]))
+    return v
+
+
+def encode_states(batch: HistoryBatch, result: ReplayResult, histories: Sequence[WorkflowHistory],
+                  shuffle_seed: Optional[int] = None, sticky: Iterable[int] = (), multi_branch: Iterable[int] = ()
+                  ) -> StateBlobSet:
+    """The persisted form of the states ``result`` holds for ``batch`` (a replay of ``histories``), canonical
+    workflow order: what the SQL store would return for each execution whose replay ended OK (any other
+    workflow has no blobs).  The execution blob comes first, then activities, timers, children,
+    request-cancels and signals in row order; ``shuffle_seed`` shuffles each execution's blobs.
+    ``sticky`` / ``multi_branch``: workflow indices given a sticky task list / a second, non-current branch."""
+    loaded = result.to_loaded(batch)
+    sticky, multi_branch = set(sticky), set(multi_branch)
+    rng = random.Random(shuffle_seed) if shuffle_seed is not None else None
+    offs = {name: np.cumsum(loaded.counts(name)) - loaded.counts(name) for name in loaded.rows}
+    workflows = []
+    for w, h in enumerate(histories):
+        ex = loaded.exec[w]
+        if not loaded.mask[w]:
+            workflows.append((0, []))
+            continue
+        names = _inverse(loaded.interners[w] if loaded.interners is not None else None)
+
+        def rows(name, n_f):
+            o = int(offs[name][w])
+            return loaded.rows[name][o:o + max(int(ex[n_f]), 0)]
+
+        src = int(ex["token_src"])
+        token = b"" if src == 0 else (thrift_history_branch_token(h.run_id, h.branch_id) if src == 1 else bytes(h.final_token))
+        items = [(int(r["event_id"]), int(r["version"])) for r in rows("vh", "n_vh_items")]
+        points = [(names[int(r["key"])], bool(int(r["flags"]) & abi.ROW_RESETTABLE)) for r in rows("rp", "n_reset_points")]
+        blobs = [(abi.STATE_EXECUTION, 0, 0, "", encode_struct("WorkflowExecutionInfo", execution_values(
+            ex, token, items, points, "sticky-tl" if w in sticky else "", w in multi_branch)))]
+        for r in rows("act", "n_activity"):
+            blobs.append((abi.STATE_ACTIVITY, int(r["schedule_id"]), to_unix_nano(r["last_heartbeat_time"]), "",
+                          encode_struct("ActivityInfo", activity_values(r, names[int(r["key"])]))))
+        for r in rows("timer", "n_timer"):
+            blobs.append((abi.STATE_TIMER, 0, 0, names[int(r["key"])], encode_struct("TimerInfo", timer_values(r))))
+        for r in rows("child", "n_child"):
+            blobs.append((abi.STATE_CHILD, int(r["initiated_id"]), 0, "", encode_struct("ChildExecutionInfo", child_values(r))))
+        for r in rows("rc", "n_rc"):
+            blobs.append((abi.STATE_REQUEST_CANCEL, int(r["initiated_id"]), 0, "",
+                          encode_struct("RequestCancelInfo", initiated_values(r, False))))
+        for r in rows("sig", "n_signal"):
+            blobs.append((abi.STATE_SIGNAL, int(r["initiated_id"]), 0, "", encode_struct("SignalInfo", initiated_values(r, True))))
+        if rng is not None:
+            rng.shuffle(blobs)
+        workflows.append((int(ex["next_event_id"]), blobs))
+    return build_blob_set(workflows)
+
+
+# ---- the loaded image -------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class LoadedImage(LoadedStates):
+    """The dense loaded image (``crr_load_image``): a ``LoadedStates`` (mask: status OK) plus the per-table
+    offsets, current branch tokens, key dictionaries, statuses and flags."""
+    offsets: Optional[np.ndarray] = None      # int64 [LOAD_TABLES, n_wf + 1]
+    tokens: Optional[np.ndarray] = None       # uint8
+    key_off: Optional[np.ndarray] = None      # uint64 into key_bytes
+    key_len: Optional[np.ndarray] = None
+    key_bytes: Optional[np.ndarray] = None
+    status: Optional[np.ndarray] = None       # int32 abi.LoadStatus
+    flags: Optional[np.ndarray] = None        # uint32 LOAD_FLAG_*
+    err_blob: int = -1                        # lowest malformed blob index
+
+    def token(self, w: int) -> bytes:
+        o = self.offsets[abi.LOAD_T_TOKEN]
+        return self.tokens[int(o[w]):int(o[w + 1])].tobytes()
+
+    def keys(self, w: int) -> List[str]:
+        """Key id k's string at index k - 1."""
+        o = self.offsets[abi.LOAD_T_KEYS]
+        kb = self.key_bytes
+        return [kb[int(self.key_off[k]):int(self.key_off[k]) + int(self.key_len[k])].tobytes().decode()
+                for k in range(int(o[w]), int(o[w + 1]))]
+
+    def resumable(self, mask=None) -> LoadedStates:
+        """The states to resume as ``flatten(..., loaded=)`` takes them: the workflows in ``mask`` that loaded OK;
+        the others' exec rows zeroed and their rows dropped (what ``ReplayResult.to_loaded`` does)."""
+        m = self.mask if mask is None else (self.mask & np.asarray(mask, bool))
+        ex = self.exec.copy()
+        ex[~m] = np.zeros(1, abi.EXEC_ROW)
+        rows = {name: self.rows[name][np.repeat(m, self.counts(name))].copy() for name in abi.LOAD_ROW_TABLES}
+        return LoadedStates(ex, rows, m, self.interners)
+
+    def image_bytes(self) -> Dict[str, bytes]:
+        """Every buffer of the image as bytes (host against device comparisons)."""
+        out = {"exec": self.exec.tobytes(), "offsets": self.offsets.tobytes(), "tokens": self.tokens.tobytes(),
+               "key_off": self.key_off.tobytes(), "key_len": self.key_len.tobytes(), "key_bytes": self.key_bytes.tobytes(),
+               "status": self.status.tobytes(), "flags": self.flags.tobytes()}
+        out.update({name: self.rows[name].tobytes() for name in abi.LOAD_ROW_TABLES})
+        return out
+
+
+_ROW_DTYPES = {t[0]: t[1] for t in abi.TABLES}
+
+
+class _ImageBuffers:
+    """Host buffers of a ``crr_load_image`` sized from a summary."""
+
+    def __init__(self, S: abi.CLoadSummary):
+        n = int(S.n_wf)
+        tot = [int(x) for x in S.totals]
+        self.exec = np.zeros(n, abi.EXEC_ROW)
+        self.rows = {name: np.zeros(tot[t], _ROW_DTYPES[name]) for t, name in enumerate(abi.LOAD_ROW_TABLES)}
+        self.offsets = np.zeros((abi.LOAD_TABLES, n + 1), np.int64)
+        self.tokens = np.zeros(tot[abi.LOAD_T_TOKEN], np.uint8)
+        self.key_off = np.zeros(tot[abi.LOAD_T_KEYS], np.uint64)
+        self.key_len = np.zeros(tot[abi.LOAD_T_KEYS], np.uint32)
+        self.key_bytes = np.zeros(tot[abi.LOAD_T_KEY_BYTES], np.uint8)
+        self.status = np.zeros(n, np.int32)
+        self.flags = np.zeros(n, np.uint32)
+        self.c = abi.CLoadImage()
+
+        def ptr(a):
+            return a.ctypes.data if a.size else None
+        self.c.exec = ptr(self.exec)
+        for t, name in enumerate(abi.LOAD_ROW_TABLES):
+            self.c.rows[t] = ptr(self.rows[name])
+        for f in ("offsets", "tokens", "key_off", "key_len", "key_bytes", "status", "flags"):
+            setattr(self.c, f, ptr(getattr(self, f)))
+
+    def image(self, S: abi.CLoadSummary) -> LoadedImage:
+        img = LoadedImage(self.exec, self.rows, self.status == 0, None, self.offsets, self.tokens, self.key_off,
+                          self.key_len, self.key_bytes, self.status, self.flags, int(S.err_blob))
+        img.interners = [dict([("", 0)] + [(s, k + 1) for k, s in enumerate(img.keys(w))]) for w in range(int(S.n_wf))]
+        return img
+
+
+def _c_batch(sbs: StateBlobSet, ptr) -> abi.CStateBatch:
+    c = abi.CStateBatch()
+    c.bytes, c.blob_off, c.blob, c.wf, c.strings = (ptr(sbs.bytes), ptr(sbs.blob_off), ptr(sbs.blob), ptr(sbs.wf),
+                                                    ptr(sbs.strings))
+    c.n_blobs, c.n_wf = sbs.n_blobs, sbs.n_wf
+    return c
+
+
+def _host_lib():
+    from . import decode
+    L = decode.lib()
+    if not getattr(L, "_load_bound", False):
+        vp = ctypes.c_void_p
+        L.crr_load_states_host.argtypes = [vp, vp, vp, ctypes.c_int]
+        L.crr_load_states_host.restype = ctypes.c_int
+        L._load_bound = True
+    return L
+
+
+def load_states_host(sbs: StateBlobSet, threads: int = 1) -> LoadedImage:
+    """Decode with the host restatement (``crr_load_states_host``); ``interners`` come from the dictionaries."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    S = abi.CLoadSummary()
+    rc = L.crr_load_states_host(ctypes.byref(c), None, ctypes.byref(S), threads)   # sizes
+    if rc != 0:
+        raise RuntimeError(f"crr_load_states_host failed: {rc}")
+    buf = _ImageBuffers(S)
+    rc = L.crr_load_states_host(ctypes.byref(c), ctypes.byref(buf.c), ctypes.byref(S), threads)
+    if rc != 0:
+        raise RuntimeError(f"crr_load_states_host failed: {rc}")
+    return buf.image(S)
+
+
+@dataclasses.dataclass
+class DeviceStates:
+    """A StateBlobSet resident in HBM."""
+    blobs: StateBlobSet
+    tensors: Dict[str, object]
+    c: abi.CStateBatch
+
+
+class StateLoader:
+    """The device loader: ``upload`` the persisted bytes, ``plan`` (decode into the scratch), then ``read`` the
+    dense image back or ``place`` it into a resumed batch's outputs.  No host fallback: a missing library or
+    device raises."""
+
+    def __init__(self, engine):
+        self.engine = engine
+        self.torch = engine.torch
+        self.lib = engine.lib
+        vp = ctypes.c_void_p
+        L = self.lib
+        L.crr_load_scratch_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.crr_load_scratch_bytes.restype = ctypes.c_size_t
+        L.crr_load_states_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp]
+        L.crr_load_states_plan.restype = ctypes.c_int
+        L.crr_load_states_read.argtypes = [vp, ctypes.c_size_t, vp, vp, vp]
+        L.crr_load_states_read.restype = ctypes.c_int
+        L.crr_load_states_place.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, vp, vp]
+        L.crr_load_states_place.restype = ctypes.c_int
+        self.scratch = None
+        self.scratch_bytes = 0
+        self.summary = None
+        self.grown = 0          # the size the last plan grew the scratch to (0: it fitted)
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.engine.dev).cuda_stream)
+
+    def upload(self, sbs: StateBlobSet) -> DeviceStates:
+        from .engine import _dev_bytes
+        T = {f: _dev_bytes(self.torch, getattr(sbs, f), self.engine.dev, pad=abi.INGEST_PAD)
+             for f in ("bytes", "blob_off", "blob", "wf", "strings")}
+        return DeviceStates(sbs, T, self._c(sbs, T))
+
+    @staticmethod
+    def _c(sbs, T):
+        c = abi.CStateBatch()
+        for f in ("bytes", "blob_off", "blob", "wf", "strings"):
+            setattr(c, f, T[f].data_ptr())
+        c.n_blobs, c.n_wf = sbs.n_blobs, sbs.n_wf
+        return c
+
+    def _alloc(self, size: int):
+        self.scratch = self.torch.empty(size + 16, dtype=self.torch.uint8, device=self.engine.dev)
+        self.scratch_bytes = size
+
+    def plan(self, ds: DeviceStates, scratch_bytes: Optional[int] = None) -> abi.CLoadSummary:
+        """Decode; a scratch that proves too small is grown once to what the plan asked for."""
+        want = int(scratch_bytes if scratch_bytes is not None else
+                   self.lib.crr_load_scratch_bytes(ds.c.n_blobs, ds.c.n_wf))
+        if self.scratch is None or self.scratch_bytes < want or scratch_bytes is not None:
+            self._alloc(want)
+        S = abi.CLoadSummary()
+        self.grown = 0
+        for _ in range(2):
+            rc = self.lib.crr_load_states_plan(ctypes.byref(ds.c), ctypes.c_void_p(self.scratch.data_ptr()),
+                                               ctypes.c_size_t(self.scratch_bytes), ctypes.byref(S), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"crr_load_states_plan failed: {rc}")
+            if S.err != abi.SCRATCH_TOO_SMALL:
+                break
+            self.grown = int(S.scratch_needed)
+            self._alloc(self.grown)
+        if S.err != 0:
+            raise RuntimeError(f"crr_load_states_plan: err {S.err}")
+        self.summary = S
+        return S
+
+    def read(self) -> LoadedImage:
+        """The last plan's dense image, copied to the host."""
+        S = self.summary
+        buf = _ImageBuffers(S)
+        rc = self.lib.crr_load_states_read(ctypes.c_void_p(self.scratch.data_ptr()), ctypes.c_size_t(self.scratch_bytes),
+                                           ctypes.byref(S), ctypes.byref(buf.c), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_states_read failed: {rc}")
+        self.torch.cuda.synchronize(self.engine.dev)
+        return buf.image(S)
+
+    def place(self, db, perm: Optional[np.ndarray] = None):
+        """Scatter the last plan's image into ``db``'s outputs (an ``engine.DeviceBatch``): device position p takes
+        loaded workflow ``perm[p]`` (default: the batch's own ``perm``, identity for a canonical batch)."""
+        if perm is None:
+            perm = db.batch.perm
+        p_ptr = None
+        if perm is not None:
+            db.tensors["load_perm"] = self.torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int64).astype(np.int32)).to(self.engine.dev)
+            p_ptr = db.tensors["load_perm"].data_ptr()
+        rc = self.lib.crr_load_states_place(ctypes.c_void_p(self.scratch.data_ptr()), ctypes.c_size_t(self.scratch_bytes),
+                                            ctypes.byref(self.summary), ctypes.byref(db.c_in), ctypes.c_void_p(p_ptr),
+                                            ctypes.byref(db.c_out), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_states_place failed: {rc}")
