@@ -3083,6 +3083,77 @@ struct LaneSource {
   __device__ __forceinline__ i64 task_id(i32 step) const { return E.task_id[ix(step)]; }
 };
 
+// LaneSource for a wavefront whose lanes hold one wave-interleaved group (stride 64, begin - lane wave-uniform;
+// replay_lds).  The lanes still in the lane loop share the step, so a step's element index is scalar -- the
+// group's base plus step * 64, kept 64-bit -- and each column load is a scalar row pointer plus the thread's
+// byte offset (below 2 KB): no per-lane 64-bit address chain, and the seven column pointers stay in scalar
+// registers across the loop instead of being reloaded from the kernel arguments before every load.  Gathered
+// lanes (the retry pass, the general path) and the tiers whose segment may start off a group boundary keep
+// LaneSource's per-lane form.
+// Deciding the typed loads by scalar branches when the next type is wave-uniform (a second copy of the four
+// predicated loads) measured inside the run-to-run spread on config 2 (0.4237 against 0.4282 ms, medians
+// overlapping) and is not built.
+struct WaveLaneSource : LaneSource {
+  i64 ubase;  // begin - threadIdx.x: the group's first element less the wavefront's offset in the block (scalar)
+  __device__ __forceinline__ WaveLaneSource(const crr_events& e, i64 b, i32 count, bool tasks)
+      : LaneSource(e, b, 64, count, tasks), ubase(uniform64(b - (i64)threadIdx.x)) {}
+  // element `step` (wave-uniform) of a column
+  template <class T>
+  __device__ __forceinline__ T at(const T* col, i32 step) const {
+    static_assert(sizeof(T) == 1 || sizeof(T) == 4 || sizeof(T) == 8, "column width");
+    // the row pointer is read back as a scalar before the thread's offset is added: otherwise the compiler
+    // regroups the sum as (column + thread offset) + step offset and keeps one 64-bit per-lane base per
+    // column across the loop (14 VGPRs, which the 168-register budget spills)
+    const i64 row = uniform64((i64)reinterpret_cast<uintptr_t>(col + (ubase + (i64)step * 64)));
+    // The thread's byte offset, one VALU instruction beside the load.  Opaque and tied to the step (the
+    // unused operand), so it is not hoisted out of the loop: hoisted, the offsets would be live across the
+    // loop widened to 64 bits, and the load would lose the scalar-base form -- global_load v, v_off, s[..]
+    // -- which takes a 32-bit offset register defined in the load's own block.
+    u32 off;
+    if constexpr (sizeof(T) == 1) asm("v_mov_b32 %0, %1 ; step %2" : "=v"(off) : "v"(threadIdx.x), "s"(step));
+    else if constexpr (sizeof(T) == 4) asm("v_lshlrev_b32 %0, 2, %1 ; step %2" : "=v"(off) : "v"(threadIdx.x), "s"(step));
+    else asm("v_lshlrev_b32 %0, 3, %1 ; step %2" : "=v"(off) : "v"(threadIdx.x), "s"(step));
+    // a global-address-space pointer: a plain one rebuilt from an integer would be a flat access
+    typedef const T __attribute__((address_space(1))) * global_ptr;
+    return *(global_ptr)((u64)row + (u64)off);
+  }
+  __device__ __forceinline__ Ev load(i32 step, u32 et) const {
+    Ev e;
+    e.et = et;
+    e.id_ = at(E.event_id, step);
+    e.ver_ = at(E.version, step);
+    e.ts_ = need::has(ts_mask, et) ? at(E.timestamp, step) : 0;
+    e.ref_ = need::has(need::kRef, et) ? at(E.ref, step) : 0;
+    e.key_ = need::has(need::kKey, et) ? at(E.key, step) : 0u;
+    e.aux_ = need::has(aux_mask, et) ? at(E.aux, step) : 0;
+    e.task_ = 0;
+    return e;
+  }
+  __device__ __forceinline__ void start() {
+    if (n > 0) {
+      nx.et = at(E.etype, 0);
+      et_nx = E.etype[ix(n > 1 ? 1 : 0)];
+      nx.id_ = at(E.event_id, 0);
+      nx.ver_ = at(E.version, 0);
+      nx.ts_ = at(E.timestamp, 0);
+      nx.ref_ = at(E.ref, 0);
+      nx.key_ = at(E.key, 0);
+      nx.aux_ = at(E.aux, 0);
+      nx.task_ = 0;
+    }
+  }
+  __device__ __forceinline__ Ev next(i32 s) {
+    const Ev e = nx;
+    issue(s);
+    return e;
+  }
+  __device__ __forceinline__ void issue(i32 s) {
+    const i32 su = uniform32(s);  // the lanes still in the loop share s
+    if (s + 1 < n) nx = load(su + 1, et_nx);
+    if (s + 2 < n) et_nx = at(E.etype, su + 2);
+  }
+};
+
 // One wavefront per workflow runs the state machine on wave-uniform values.  The workflow's events
 // stream through in 64-event chunks, one event per lane (one coalesced load per column, the next chunk
 // one chunk ahead).  Per chunk the version-history prologue of all 64 events runs lane-parallel
@@ -4489,6 +4560,28 @@ __device__ __forceinline__ void replay_lds(const crr_inputs& in, const crr_outpu
                                            Digest& D) {
   static_assert(sizeof(typename WaveTier<TIER>::Arena) * kWavesPerBlock <= sizeof(LdsArena<TIER>),
                 "per-wave arenas must fit in the lane arena");
+  const u32 n_lane = WAVE_TAIL ? lane_count(in) : in.n_wf;
+  const u32 tail_end = WAVE_TAIL ? tail_count_end(in) : in.n_wf;  // [tail_end, n_wf): replay_big_kernel
+  const u32 wave_blocks = WAVE_TAIL ? (tail_end - n_lane + kWavesPerBlock - 1) / kWavesPerBlock : 0;
+  const bool lane_block = !WAVE_TAIL || blockIdx.x >= wave_blocks;
+  const u32 w = lo + (blockIdx.x - wave_blocks) * kBlock + threadIdx.x;  // lanes [lo, hi); launched with kBlock
+  const bool in_range = lane_block && w < hi;
+  const crr_workflow* wfp = in.wf + w;
+  // The lane workflow's descriptor in one round trip, issued before the CRC tables are built: the round
+  // trip overlaps the build's barrier phases (the tables are first read at the checksum, after the loop).
+  // The phase test and the early returns stay below the last barrier.
+  Geo G{};
+  G.out = out;  // uniform on every path (set inside the branch alone, the row pointers would be per-lane values)
+  G.st = 64;
+  i64 ev_begin0 = 0;
+  i32 ev_count0 = 0;
+  u32 wf_flags = 0;
+  if (in_range) {
+    load_geo(G, wfp, out, 64);
+    ev_begin0 = wfp->ev_begin;
+    ev_count0 = wfp->ev_count;
+    wf_flags = wfp->flags;
+  }
 #if CRR_SMALL_CRC == 2
   const u32* crc_tables = kCrcGlobal.v;  // gathers through the L1
 #else
@@ -4506,43 +4599,41 @@ __device__ __forceinline__ void replay_lds(const crr_inputs& in, const crr_outpu
 #endif
 #endif
   __shared__ BlockArena<TIER> arena;
-  const u32 n_lane = WAVE_TAIL ? lane_count(in) : in.n_wf;
-  const u32 tail_end = WAVE_TAIL ? tail_count_end(in) : in.n_wf;  // [tail_end, n_wf): replay_big_kernel
-  const u32 wave_blocks = WAVE_TAIL ? (tail_end - n_lane + kWavesPerBlock - 1) / kWavesPerBlock : 0;
-  if (WAVE_TAIL && blockIdx.x < wave_blocks) {
+  if (WAVE_TAIL && !lane_block) {
     const u32 wv = (u32)uniform32((i32)(threadIdx.x >> 6));
-    const u32 w = n_lane + blockIdx.x * kWavesPerBlock + wv;
-    if (w >= tail_end) return;
-    const crr_workflow* wfp = in.wf + w;
-    if (((wfp->flags & CRR_WF_FLAG_NEW_RUN) != 0) != (phase == 0)) return;
-    Geo G;
-    load_geo(G, wfp, out, 1);
+    const u32 wt = n_lane + blockIdx.x * kWavesPerBlock + wv;
+    if (wt >= tail_end) return;
+    const crr_workflow* wtp = in.wf + wt;
+    if (((wtp->flags & CRR_WF_FLAG_NEW_RUN) != 0) != (phase == 0)) return;
+    Geo GT;
+    load_geo(GT, wtp, out, 1);
     WaveLds<typename WaveTier<TIER>::Arena, 1> T;  // outgrown: the retry pass's wave list
     bind_arena(T, &arena.wave[wv]);
     T.init();
 
-    WaveSource S(in.ev, wfp->ev_begin, 1, wfp->ev_count);
-    replay_body<EMIT>(in, out, w, wfp, G, T, S, crc_tables, nullptr, &D);
+    WaveSource S(in.ev, wtp->ev_begin, 1, wtp->ev_count);
+    replay_body<EMIT>(in, out, wt, wtp, GT, T, S, crc_tables, nullptr, &D);
     return;
   }
-  const u32 w = lo + (blockIdx.x - wave_blocks) * kBlock + threadIdx.x;  // lanes [lo, hi); launched with kBlock
-  if (w >= hi) return;
-  const crr_workflow* wfp = in.wf + w;
-  // the descriptor in one round trip: the phase test reads its flags after the geometry is loaded
+  if (!in_range) return;
   const i64 lane = threadIdx.x & 63;
-  Geo G;
-  load_geo(G, wfp, out, 64);
-  const i64 ev_begin0 = wfp->ev_begin;
-  const i32 ev_count0 = wfp->ev_count;
-  const u32 wf_flags = wfp->flags;
-  asm volatile("" ::"v"(ev_begin0), "v"(ev_count0), "v"(wf_flags));  // all issued before the phase test's wait
+  asm volatile("" ::"v"(ev_begin0), "v"(ev_count0), "v"(wf_flags));  // all arrived before the phase test
   if (((wf_flags & CRR_WF_FLAG_NEW_RUN) != 0) != (phase == 0)) return;
   uniformize_geo(G, lane);
   const i64 ev_begin = uniform64(ev_begin0 - lane) + lane;
   LdsTables<TIER, LANES> T;
   T.init(&arena.lane, &in, ev_begin);
-  LaneSource S(in.ev, ev_begin, 64, wfp->ev_count, EMIT && (in.flags & CRR_IN_EMIT_TASKS) != 0);
-  replay_body<EMIT>(in, out, w, wfp, G, T, S, crc_tables, nullptr, &D);
+  const bool tasks = EMIT && (in.flags & CRR_IN_EMIT_TASKS) != 0;
+  if constexpr (LANES) {
+    // the divergent dispatch holds more scalar state across the loop: with the seven column pointers beside it
+    // the register allocator parks 13 SGPRs in VGPR lanes and the private segment grows (24 -> 80 B)
+    LaneSource S(in.ev, ev_begin, 64, wfp->ev_count, tasks);
+    replay_body<EMIT>(in, out, w, wfp, G, T, S, crc_tables, nullptr, &D);
+  } else {
+    // the wavefront is one interleaved group: scalar column rows
+    WaveLaneSource S(in.ev, ev_begin, wfp->ev_count, tasks);
+    replay_body<EMIT>(in, out, w, wfp, G, T, S, crc_tables, nullptr, &D);
+  }
 }
 template <bool WAVE_TAIL, bool EMIT, bool LANES = false>
 #ifndef CRR_SMALL_WAVES_PER_EU
