@@ -305,6 +305,23 @@ class CLoadImage(ctypes.Structure):
                 ("key_bytes", ctypes.c_void_p), ("status", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
 
 
+# ---- checksum verification of loaded states (include/cadence_load_verify.h) ------------------------------
+STORED_CHECKSUM = np.dtype([("version", "<i4"), ("flavor", "<i4"), ("value", "<u4"), ("value_len", "<u4")])
+VERIFY_ROW = np.dtype([("computed", "<u4"), ("outcome", "<i4"), ("payload_len", "<u4"), ("reserved", "<u4")])
+CHECKSUM_PAYLOAD_V1 = 1                       # mutableStateChecksumPayloadV1
+CHECKSUM_FLAVOR_CRC32 = 1                     # FlavorIEEECRC32OverThriftBinary
+
+
+class VerifyOutcome(enum.IntEnum):
+    MATCH = 0
+    MISMATCH = 1
+    NONE = 2
+    INVALIDATED = 3
+    BAD_VERSION = 4
+    BAD_FLAVOR = 5
+    NOT_LOADED = 6
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -372,7 +389,7 @@ def check_layout(lib):
         got = lib.crr_sizeof(i)
         if got != dt.itemsize:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {got} vs numpy {dt.itemsize}")
-    for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize)):
+    for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
     for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage)):

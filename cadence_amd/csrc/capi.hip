@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "cadence_load.h"
+#include "cadence_load_verify.h"
 #include "cadence_replay.h"
 #include "stream_device.h"
 
@@ -257,6 +258,8 @@ size_t crr_sizeof(int which) {
     case 17: return sizeof(crr_state_batch);
     case 18: return sizeof(crr_load_summary);
     case 19: return sizeof(crr_load_image);
+    case 20: return sizeof(crr_stored_checksum);
+    case 21: return sizeof(crr_verify_row);
     default: return 0;
   }
 }

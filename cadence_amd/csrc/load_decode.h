@@ -11,6 +11,8 @@
 //                              CRR_ROW_MAPPED, version-history items, token bytes, reset points
 //   (scan B)                   dictionary entries and bytes
 //   dict_wf      per workflow  the dictionary's key_off / key_len / bytes
+//   verify_wf    per workflow  (on request, cadence_load_verify.h) the mutable-state checksum payload's CRC from
+//                              the dense image and the persisted bytes, compared with the stored checksum
 //
 // Wire format: thrift binary (big-endian; field header = type byte + i16 id, 0 ends a struct), field IDs of
 // .gen/go/sqlblobs/sqlblobs.go restated below (tests/golden/sqlblobs_fields.json pins them); a field whose
@@ -24,6 +26,7 @@
 #include <string.h>
 
 #include "cadence_load.h"
+#include "cadence_load_verify.h"
 
 #if defined(__HIPCC__)
 #define CRR_HD __host__ __device__ inline
@@ -220,6 +223,11 @@ struct ExecAux {
   uint32_t vh_len, rp_len;
   int32_t exec_idx;   // index of the execution blob within the workflow
   int32_t current;    // current version-history index
+  // what only the checksum payload needs (verify_wf): the sticky task list's name, every branch, the cut-off's time
+  uint64_t sticky_off;
+  int64_t last_updated;   // LastUpdatedTimeNanos as stored (absent: 0)
+  uint32_t sticky_len;
+  int32_t n_hist;
 };
 
 CRR_HD uint64_t align16(uint64_t x) { return (x + 15u) & ~15ull; }
@@ -409,19 +417,40 @@ struct VhWalk {
   uint32_t tok_len;
 };
 
+// one shared.VersionHistoryItem{10 eventID, 20 version}, the cursor at its first field
+CRR_HD crr_vh_item read_vh_item(Rd& r, Frame* stk) {
+  crr_vh_item it = {0, 0};
+  uint8_t t;
+  int16_t id;
+  while (next_field(r, t, id)) {
+    if (id == 10 && t == T_I64) it.event_id = rd_i64(r);
+    else if (id == 20 && t == T_I64) it.version = rd_i64(r);
+    else skip(r, t, stk);
+  }
+  return it;
+}
+
+struct VhNoVisit {
+  CRR_HD void operator()(uint64_t, uint32_t, uint64_t, int32_t) const {}
+};
+
 // shared.VersionHistories{10 currentVersionHistoryIndex, 20 list<VersionHistory{10 branchToken,
 // 20 list<VersionHistoryItem{10 eventID, 20 version}>}>} behind the 0x59 preamble; items of history `target`
 // go to `items` (NULL: counted only).  false: malformed (a repeated list field included, so that every
 // index written here stays below the count an earlier walk returned).
-CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame* stk) {
+// `vis(token offset, token length, items position, item count)` is called once per history, in stored order,
+// when its struct ends: the token as its last field 10 gave it (absent: length 0), the items as the cursor
+// behind the list's header and the element count (absent: 0), to be read again with read_vh_item.
+template <class Vis>
+CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame* stk, Vis&& vis) {
   out.current = 0;
   out.n_hist = 0;
   out.n_items = 0;
   out.tok_off = 0;
   out.tok_len = 0;
   if (rd_u8(r) != 0x59) return false;
-  uint8_t t, t2, t3;
-  int16_t id, id2, id3;
+  uint8_t t, t2;
+  int16_t id, id2;
   bool seen_histories = false;
   while (next_field(r, t, id)) {
     if (id == 10 && t == T_I32) {
@@ -435,27 +464,25 @@ CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame
       for (int32_t h = 0; h < n; ++h) {
         const bool mine = out.n_hist == target;
         bool seen_items = false;
+        uint64_t tok_off = 0, items_pos = 0;
+        uint32_t tok_len = 0;
+        int32_t n_items = 0;
         while (next_field(r, t2, id2)) {
           if (id2 == 10 && t2 == T_STRING) {
-            uint64_t o;
-            uint32_t l;
-            rd_str(r, o, l);
+            rd_str(r, tok_off, tok_len);
             if (mine) {
-              out.tok_off = o;
-              out.tok_len = l;
+              out.tok_off = tok_off;
+              out.tok_len = tok_len;
             }
           } else if (id2 == 20 && t2 == T_LIST) {
             const uint8_t et2 = rd_u8(r);
             const int32_t m = rd_i32(r);
             if (r.bad || seen_items || et2 != T_STRUCT || m < 0 || (uint64_t)m > r.end - r.pos) return false;
             seen_items = true;
+            items_pos = r.pos;
+            n_items = m;
             for (int32_t k = 0; k < m; ++k) {
-              crr_vh_item it = {0, 0};
-              while (next_field(r, t3, id3)) {
-                if (id3 == 10 && t3 == T_I64) it.event_id = rd_i64(r);
-                else if (id3 == 20 && t3 == T_I64) it.version = rd_i64(r);
-                else skip(r, t3, stk);
-              }
+              const crr_vh_item it = read_vh_item(r, stk);
               if (r.bad) return false;
               if (mine) {
                 if (items) items[out.n_items] = it;
@@ -467,6 +494,7 @@ CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame
           }
         }
         if (r.bad) return false;
+        vis(tok_off, tok_len, items_pos, n_items);
         ++out.n_hist;
       }
     } else {
@@ -474,6 +502,10 @@ CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame
     }
   }
   return !r.bad;
+}
+
+CRR_HD bool walk_vh(Rd r, int32_t target, crr_vh_item* items, VhWalk& out, Frame* stk) {
+  return walk_vh(r, target, items, out, stk, VhNoVisit());
 }
 
 // shared.ResetPoints{10 list<ResetPointInfo{10 binaryChecksum, 20 runID, 30 firstDecisionCompletedID,
@@ -515,7 +547,6 @@ CRR_HD bool walk_reset_points(Rd r, Frame* stk, Fn&& fn) {
 struct ExecParse {
   uint64_t vh_enc_off, rp_enc_off;
   uint32_t vh_enc_len, rp_enc_len;
-  bool sticky;
 };
 
 // sqlblobs.WorkflowExecutionInfo -> the exec row (persistence_mapper.go ToInternalWorkflowExecutionInfo)
@@ -537,6 +568,7 @@ CRR_HD bool parse_execution(Rd& r, Frame* stk, int32_t idx, crr_exec_row& R, Exe
       CRR_F(48, T_I64, R.last_event_task_id = rd_i64(r))
       CRR_F(50, T_I64, R.last_first_event_id = rd_i64(r))
       CRR_F(52, T_I64, R.last_processed_event = rd_i64(r))
+      CRR_F(56, T_I64, A.last_updated = rd_i64(r))
       CRR_F(58, T_I64, R.decision_version = rd_i64(r))
       CRR_F(60, T_I64, R.decision_schedule_id = rd_i64(r))
       CRR_F(62, T_I64, R.decision_started_id = rd_i64(r))
@@ -556,15 +588,7 @@ CRR_HD bool parse_execution(Rd& r, Frame* stk, int32_t idx, crr_exec_row& R, Exe
           skip(r, t, stk);
         }
         break;
-      case 78:
-        if (t == T_STRING) {
-          uint64_t o;
-          uint32_t l;
-          if (rd_str(r, o, l)) P.sticky = l != 0;
-        } else {
-          skip(r, t, stk);
-        }
-        break;
+      CRR_F(78, T_STRING, rd_str(r, A.sticky_off, A.sticky_len))
       case 94:   // ExpirationTime: 0 in the row when unset or the zero time
         if (t == T_I64) {
           const int64_t v = rd_i64(r);
@@ -700,6 +724,7 @@ CRR_HD void count_wf(const Ctx& c, uint32_t w, Frame* stk) {
   }
   if (st == CRR_LOAD_OK) {
     A.current = V.current;
+    A.n_hist = V.n_hist;
     cnt[5] = V.n_items;
     cnt[CRR_LOAD_T_TOKEN] = V.tok_len;
     R.next_event_id = W.next_event_id;
@@ -712,7 +737,7 @@ CRR_HD void count_wf(const Ctx& c, uint32_t w, Frame* stk) {
     R.n_reset_points = (int32_t)cnt[6];
     R.token_src = V.tok_len ? 1 : 0;
     R.src_next = (int32_t)n;
-    if (P.sticky) fl |= CRR_LOAD_FLAG_STICKY;
+    if (A.sticky_len) fl |= CRR_LOAD_FLAG_STICKY;
     if (V.n_hist > 1) fl |= CRR_LOAD_FLAG_MULTI_BRANCH;
   } else {
     memset(&R, 0, sizeof R);
@@ -835,6 +860,174 @@ CRR_HD void dict_wf(const Ctx& c, uint32_t w) {
     for (uint32_t q = 0; q < len; ++q) d[q] = s[q];
     run += len;
   }
+}
+
+// ---- per workflow: the checksum Load verifies (cadence_load_verify.h) --------------------------------------
+// CRC32-IEEE (hash/crc32.ChecksumIEEE, common/checksum/crc.go:46), slicing-by-8: the streaming writer of
+// replay_kernel.hip's payload_crc restated for both builds.  The tables are 8 x 256 words: in LDS on the
+// device (build_crc_tables in load_kernel.hip), a constant on the host (make_crc_tab).
+struct CrcTab {
+  uint32_t v[8 * 256];
+};
+constexpr CrcTab make_crc_tab() {
+  CrcTab T{};
+  for (uint32_t i = 0; i < 256; ++i) {
+    uint32_t c = i;
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+    T.v[i] = c;
+  }
+  for (int t = 1; t < 8; ++t)
+    for (int i = 0; i < 256; ++i) {
+      const uint32_t p = T.v[(t - 1) * 256 + i];
+      T.v[t * 256 + i] = (p >> 8) ^ T.v[p & 0xff];
+    }
+  return T;
+}
+
+struct Crc {
+  const uint32_t* T;
+  uint32_t crc;
+  uint64_t buf;   // the bytes not yet folded in, in arrival order from the low byte
+  int nbuf;
+  uint32_t len;
+
+  CRR_HD void init(const uint32_t* tables) {
+    T = tables;
+    crc = 0xFFFFFFFFu;
+    buf = 0;
+    nbuf = 0;
+    len = 0;
+  }
+  CRR_HD void block8(uint64_t b) {
+    const uint32_t lo = (uint32_t)b ^ crc, hi = (uint32_t)(b >> 32);
+    crc = T[7 * 256 + (lo & 0xff)] ^ T[6 * 256 + ((lo >> 8) & 0xff)] ^ T[5 * 256 + ((lo >> 16) & 0xff)] ^
+          T[4 * 256 + (lo >> 24)] ^ T[3 * 256 + (hi & 0xff)] ^ T[2 * 256 + ((hi >> 8) & 0xff)] ^
+          T[1 * 256 + ((hi >> 16) & 0xff)] ^ T[0 * 256 + (hi >> 24)];
+  }
+  // k (1..8) bytes held in arrival order in the low bytes of d
+  CRR_HD void push(uint64_t d, int k) {
+    len += (uint32_t)k;
+    if (k < 8) d &= (1ull << (8 * k)) - 1ull;
+    if (nbuf + k < 8) {
+      buf |= d << (8 * nbuf);
+      nbuf += k;
+      return;
+    }
+    const int take = 8 - nbuf;
+    block8(nbuf ? (buf | (d << (8 * nbuf))) : d);
+    const int rem = k - take;
+    buf = rem ? (d >> (8 * take)) : 0ull;
+    nbuf = rem;
+  }
+  CRR_HD void u8(uint32_t b) { push(b & 0xff, 1); }
+  CRR_HD void be16(uint32_t v) { push(((v >> 8) & 0xff) | ((v & 0xff) << 8), 2); }
+  CRR_HD void be32(uint32_t v) { push(__builtin_bswap32(v), 4); }
+  CRR_HD void be64(int64_t v) { push(__builtin_bswap64((uint64_t)v), 8); }
+  // thrift binary field header: type byte + big-endian i16 id
+  CRR_HD void field(uint32_t type, uint32_t id) { push(type | (((id >> 8) & 0xff) << 8) | ((id & 0xff) << 16), 3); }
+  CRR_HD void list_header(uint32_t id, uint32_t elem, uint32_t n) {
+    field(T_LIST, id);
+    push(elem | ((uint64_t)__builtin_bswap32(n) << 8), 5);
+  }
+  // a binary value: its length, then its bytes (eight at a time while eight are left: no read past p + n)
+  CRR_HD void binary(const uint8_t* p, uint32_t n) {
+    be32(n);
+    uint32_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+      uint64_t d;
+      memcpy(&d, p + i, 8);
+      push(d, 8);
+    }
+    for (; i < n; ++i) u8(p[i]);
+  }
+  CRR_HD uint32_t finish() {
+    for (int i = 0; i < nbuf; ++i) crc = T[(crc ^ (uint32_t)(buf >> (8 * i))) & 0xff] ^ (crc >> 8);
+    nbuf = 0;
+    return ~crc;
+  }
+};
+
+// generateMutableStateChecksum (execution/checksum.go:36-114) for a workflow that loaded OK: 0x59 +
+// MutableStateChecksumPayload.Encode (.gen/go/checksum/checksum.go:539-821), fields and order as payload_crc
+// writes them, from the sources cadence_load_verify.h lists; then Load's decision
+// (mutable_state_builder.go:334-348).  `stored`: NULL: compute only.  Every offset used here was checked
+// against its blob's end when count_wf parsed the execution blob of the same `in`; a workflow whose recorded
+// ranges do not lie within this batch's bytes (not the planned batch) is reported as not loaded.
+CRR_HD void verify_wf(const Ctx& c, uint32_t w, const uint32_t* tables, const crr_stored_checksum* stored,
+                      int64_t invalidate_before_ns, crr_verify_row* result, Frame* stk) {
+  crr_verify_row out = {0, CRR_VERIFY_NOT_LOADED, 0, 0};
+  if (c.status()[w] != CRR_LOAD_OK) {   // (a batch without blobs, whose blob_off may be NULL, has only such workflows)
+    result[w] = out;
+    return;
+  }
+  const ExecAux A = c.aux()[w];
+  const uint64_t total = c.in.blob_off[c.in.n_blobs];
+  if (A.vh_off > total || A.vh_len > total - A.vh_off || A.sticky_off > total || A.sticky_len > total - A.sticky_off) {
+    result[w] = out;
+    return;
+  }
+  const crr_exec_row R = c.exec()[w];
+  Crc K;
+  K.init(tables);
+  K.u8(0x59);                                                                   // preambleVersion0
+  K.field(T_BOOL, 10); K.u8((R.flags & CRR_EXEC_CANCEL_REQUESTED) ? 1 : 0);     // CancelRequested
+  K.field(T_I16, 15); K.be16((uint32_t)(uint16_t)(int16_t)R.state);             // State
+  K.field(T_I64, 23); K.be64(R.last_first_event_id);
+  K.field(T_I64, 24); K.be64(R.next_event_id);
+  K.field(T_I64, 25); K.be64(R.last_processed_event);
+  K.field(T_I64, 26); K.be64((int64_t)R.signal_count);
+  K.field(T_I32, 35); K.be32((uint32_t)(int32_t)R.decision_attempt);
+  K.field(T_I64, 36); K.be64(R.decision_version);
+  K.field(T_I64, 37); K.be64(R.decision_schedule_id);
+  K.field(T_I64, 38); K.be64(R.decision_started_id);
+  // the pending-ID lists: each dense table's rows are ascending by ID (emit_wf), the ID a row's first field
+  auto ids = [&](uint32_t field_id, int t) {
+    const int64_t o = c.cnt(t)[w], n = c.cnt(t)[w + 1] - o;
+    K.list_header(field_id, T_I64, (uint32_t)n);
+    const uint8_t* row = c.rows(t) + (uint64_t)o * kRowBytes[t];
+    for (int64_t j = 0; j < n; ++j) K.be64(*reinterpret_cast<const int64_t*>(row + (uint64_t)j * kRowBytes[t]));
+  };
+  ids(45, 1);   // PendingTimerStartedIDs
+  ids(46, 0);   // PendingActivityScheduledIDs
+  ids(47, 4);   // PendingSignalInitiatedIDs
+  ids(48, 3);   // PendingReqCancelInitiatedIDs
+  ids(49, 2);   // PendingChildInitiatedIDs
+  K.field(T_STRING, 55); K.binary(c.in.bytes + A.sticky_off, A.sticky_len);      // StickyTaskListName
+  K.field(T_STRUCT, 56);                                                        // VersionHistories
+  K.field(T_I32, 10); K.be32((uint32_t)A.current);                              //   CurrentVersionHistoryIndex
+  K.list_header(20, T_STRUCT, (uint32_t)A.n_hist);                              //   Histories
+  const Rd v = {c.in.bytes, A.vh_off, A.vh_off + A.vh_len, false};
+  VhWalk V;
+  const bool ok = walk_vh(v, -1, nullptr, V, stk, [&](uint64_t tok_off, uint32_t tok_len, uint64_t items_pos, int32_t n_items) {
+    K.field(T_STRING, 10); K.binary(c.in.bytes + tok_off, tok_len);             //   VersionHistory.BranchToken
+    K.list_header(20, T_STRUCT, (uint32_t)n_items);                             //   VersionHistory.Items
+    Rd it = {v.p, items_pos, v.end, false};
+    for (int32_t k = 0; k < n_items; ++k) {
+      const crr_vh_item x = read_vh_item(it, stk);
+      K.field(T_I64, 10); K.be64(x.event_id);
+      K.field(T_I64, 20); K.be64(x.version);
+      K.u8(0);
+    }
+    K.u8(0);   // VersionHistory stop
+  });
+  if (!ok || V.n_hist != A.n_hist) {   // not the bytes the plan walked
+    result[w] = out;
+    return;
+  }
+  K.u8(0);   // VersionHistories stop
+  K.u8(0);   // payload stop
+  out.payload_len = K.len;
+  out.computed = K.finish();
+  out.outcome = CRR_VERIFY_NONE;
+  if (stored) {
+    const crr_stored_checksum S = stored[w];
+    if (S.value_len == 0) out.outcome = CRR_VERIFY_NONE;
+    else if (invalidate_before_ns > 0 && A.last_updated < invalidate_before_ns) out.outcome = CRR_VERIFY_INVALIDATED;
+    else if (S.version != CRR_CHECKSUM_PAYLOAD_V1) out.outcome = CRR_VERIFY_BAD_VERSION;
+    else if (S.flavor != CRR_CHECKSUM_FLAVOR_CRC32) out.outcome = CRR_VERIFY_BAD_FLAVOR;
+    else out.outcome = (S.value_len == 4 && S.value == out.computed) ? CRR_VERIFY_MATCH : CRR_VERIFY_MISMATCH;
+  }
+  result[w] = out;
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

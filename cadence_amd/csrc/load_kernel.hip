@@ -9,6 +9,8 @@
 //   load_emit_kernel    one lane per workflow: rows to their rank by ID, keys interned, MAPPED, items, tokens
 //   load_dict_kernel    one lane per workflow: the key dictionary
 //   load_place_kernel   one lane per device position: the dense rows scattered into a replay's slot tables
+//   load_verify_kernel  one lane per workflow: the mutable-state checksum payload generated from the dense image
+//                       and the persisted bytes, its CRC compared with the stored checksum (cadence_load_verify.h)
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -19,6 +21,7 @@
 
 #include "cadence_ingest.h"
 #include "cadence_load.h"
+#include "cadence_load_verify.h"
 #include "load_decode.h"
 #include "stream_device.h"
 
@@ -139,6 +142,35 @@ __global__ void __launch_bounds__(kBlock) load_place_kernel(Ctx c, PlaceArgs a) 
   put(4, D.sig_base, a.out.sig, a.out.live_ids[4]);
   put(5, D.vh_base, a.out.vh, nullptr);
   put(6, D.rp_base, a.out.rp, nullptr);
+}
+
+// the slicing-by-8 CRC tables of load_decode.h's Crc, built by the block in LDS (replay_kernel.hip's
+// build_crc_tables restated): table 0 the byte-wise reflected CRC32, tables 1..7 its extensions
+__device__ void build_crc_tables(uint32_t* T) {
+  for (int i = threadIdx.x; i < 256; i += kBlock) {
+    uint32_t c = (uint32_t)i;
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+    T[i] = c;
+  }
+  __syncthreads();
+  for (int t = 1; t < 8; ++t) {
+    for (int i = threadIdx.x; i < 256; i += kBlock) {
+      const uint32_t p = T[(t - 1) * 256 + i];
+      T[t * 256 + i] = (p >> 8) ^ T[p & 0xff];
+    }
+    __syncthreads();
+  }
+}
+
+// one lane per workflow: the checksum payload streamed through the CRC (nothing of it is stored), then Load's
+// decision; 16 KB of LDS per block (the tables and the skip stacks)
+__global__ void __launch_bounds__(kBlock) load_verify_kernel(Ctx c, const crr_stored_checksum* stored,
+                                                             int64_t invalidate_before_ns, crr_verify_row* result) {
+  __shared__ uint32_t crc_tables[8 * 256];
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  build_crc_tables(crc_tables);
+  const uint32_t w = blockIdx.x * kBlock + threadIdx.x;
+  if (w < c.in.n_wf) verify_wf(c, w, crc_tables, stored, invalidate_before_ns, result, stk[threadIdx.x]);
 }
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
@@ -274,6 +306,22 @@ int crr_load_states_place(const void* scratch, size_t scratch_bytes, const crr_l
   a.n_loaded = summary_host->n_wf;
   a.out = *out;
   hipLaunchKernelGGL(load_place_kernel, grid_of(a.n_pos), dim3(kBlock), 0, s, c, a);
+  return (int)hipGetLastError();
+}
+
+int crr_load_states_verify(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                           const crr_load_summary* summary_host, const crr_stored_checksum* stored,
+                           int64_t invalidate_before_ns, crr_verify_row* result, void* stream) {
+  Ctx c;
+  if (!in || !result || !plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
+  if (in->n_blobs != summary_host->n_blobs || in->n_wf != summary_host->n_wf) return -1;   // not the planned batch
+  if (in->n_blobs && (!in->bytes || !in->blob_off)) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (in->n_wf == 0) return 0;
+  c.in = *in;
+  hipLaunchKernelGGL(load_verify_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c, stored, invalidate_before_ns, result);
   return (int)hipGetLastError();
 }
 

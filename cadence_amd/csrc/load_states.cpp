@@ -2,6 +2,7 @@
 // (include/cadence_load.h).  The decoder itself is load_decode.h, the same text the gfx950 kernels of
 // load_kernel.hip compile; this file runs its phases as loops (optionally over threads), with serial
 // prefix scans between them, over a scratch laid out exactly like the device's.
+// crr_load_states_verify_host (include/cadence_load_verify.h) runs the same load, then load_decode.h's verify_wf.
 #include <stdlib.h>
 
 #include <thread>
@@ -44,11 +45,9 @@ void scan(const Ctx& c, int t) {
   p[c.in.n_wf] = run;
 }
 
-}  // namespace
-
-extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_image* dst, crr_load_summary* summary,
-                                    int threads) {
-  if (!in || !summary) return -1;
+// every phase of the load over a scratch this allocates (the caller frees c.s): 0, -1 invalid argument, -2 out of memory
+int run_load(const crr_state_batch* in, int threads, Ctx& c) {
+  c.s = nullptr;
   if (in->n_blobs && (!in->bytes || !in->blob_off || !in->blob)) return -1;
   if (in->n_wf && !in->wf) return -1;
   const uint32_t n_wf = in->n_wf;
@@ -58,7 +57,6 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
     blobs += in->wf[w].blob_count;
   }
   if (blobs != in->n_blobs) return -1;
-  Ctx c;
   c.in = *in;
   c.L = carve(in->n_blobs, n_wf, nullptr);
   uint8_t* fixed = static_cast<uint8_t*>(calloc(c.L.end + 16, 1));
@@ -75,6 +73,7 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
   uint8_t* s = static_cast<uint8_t*>(realloc(fixed, full.end + 16));
   if (!s) {
     free(fixed);
+    c.s = nullptr;
     return -2;
   }
   memset(s + c.L.end, 0, full.end + 16 - c.L.end);
@@ -84,9 +83,23 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
   scan(c, CRR_LOAD_T_KEYS);
   scan(c, CRR_LOAD_T_KEY_BYTES);
   parallel_for(n_wf, threads, [&](uint32_t w, Frame*) { dict_wf(c, w); });
+  return 0;
+}
+
+constexpr CrcTab kCrcTab = make_crc_tab();
+
+}  // namespace
+
+extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_image* dst, crr_load_summary* summary,
+                                    int threads) {
+  if (!in || !summary) return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
   int64_t totals[kCounters];
   for (int t = 0; t < kCounters; ++t) totals[t] = c.cnt(t)[n_wf];
-  fill_summary(summary, c, totals, c.err()[0], c.err()[1], full.end);
+  fill_summary(summary, c, totals, c.err()[0], c.err()[1], c.L.end);
   if (dst) {
     const size_t n = n_wf;
     if (dst->exec) memcpy(dst->exec, c.exec(), n * sizeof(crr_exec_row));
@@ -100,6 +113,19 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
     if (dst->status) memcpy(dst->status, c.status(), n * sizeof(int32_t));
     if (dst->flags) memcpy(dst->flags, c.flags(), n * sizeof(uint32_t));
   }
-  free(s);
+  free(c.s);
+  return 0;
+}
+
+extern "C" int crr_load_states_verify_host(const crr_state_batch* in, const crr_stored_checksum* stored,
+                                           int64_t invalidate_before_ns, crr_verify_row* result, int threads) {
+  if (!in || (in->n_wf && !result)) return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  parallel_for(in->n_wf, threads, [&](uint32_t w, Frame* stk) {
+    verify_wf(c, w, kCrcTab.v, stored, invalidate_before_ns, result, stk);
+  });
+  free(c.s);
   return 0;
 }

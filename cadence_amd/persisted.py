@@ -12,6 +12,10 @@ blobs; it is the reference encoder for a cgo shim's tests.
 ``StateLoader`` with the device implementation (``crr_load_states_plan`` / ``_read`` / ``_place``,
 ``include/cadence_load.h``).  Both return the dense loaded image as a ``LoadedImage`` (a
 ``flatten.LoadedStates`` plus tokens, dictionaries, statuses and flags).
+
+``StateLoader.verify`` / ``load_states_verify_host`` make the check ``mutableStateBuilder.Load`` makes right
+after materialising a state -- the stored ``checksum.Checksum`` against a freshly generated payload
+(``include/cadence_load_verify.h``) -- for every state that loaded OK, sticky and multi-branch ones included.
 """
 from __future__ import annotations
 
@@ -433,6 +437,8 @@ def _host_lib():
         vp = ctypes.c_void_p
         L.crr_load_states_host.argtypes = [vp, vp, vp, ctypes.c_int]
         L.crr_load_states_host.restype = ctypes.c_int
+        L.crr_load_states_verify_host.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int]
+        L.crr_load_states_verify_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -452,6 +458,43 @@ def load_states_host(sbs: StateBlobSet, threads: int = 1) -> LoadedImage:
     return buf.image(S)
 
 
+def stored_checksums(entries: Sequence) -> np.ndarray:
+    """``abi.STORED_CHECKSUM`` rows from ``(version, flavor, value bytes)`` tuples (``checksum.Checksum``); ``None``
+    or an empty value: none stored (``value_len`` 0).  A value of four bytes is read big-endian (crc.go:47-53);
+    one of another length keeps its length only, which is all a mismatch needs."""
+    out = np.zeros(len(entries), abi.STORED_CHECKSUM)
+    for i, e in enumerate(entries):
+        if e is None:
+            continue
+        version, flavor, value = e
+        value = bytes(value or b"")
+        out[i] = (int(version), int(flavor), struct.unpack(">I", value)[0] if len(value) == 4 else 0, len(value))
+    return out
+
+
+def _stored_array(stored, n_wf: int) -> Optional[np.ndarray]:
+    if stored is None:
+        return None
+    a = np.ascontiguousarray(stored, dtype=abi.STORED_CHECKSUM)
+    if a.shape != (n_wf,):
+        raise ValueError(f"stored: {a.shape} rows for {n_wf} workflows")
+    return a
+
+
+def load_states_verify_host(sbs: StateBlobSet, stored=None, invalidate_before_ns: int = 0, threads: int = 1) -> np.ndarray:
+    """The check ``mutableStateBuilder.Load`` makes of every state of ``sbs`` (``crr_load_states_verify_host``):
+    ``abi.VERIFY_ROW`` per workflow.  ``stored``: ``abi.STORED_CHECKSUM`` rows (``stored_checksums``); None: compute only."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    st = _stored_array(stored, sbs.n_wf)
+    out = np.zeros(sbs.n_wf, abi.VERIFY_ROW)
+    rc = L.crr_load_states_verify_host(ctypes.byref(c), st.ctypes.data if st is not None and st.size else None,
+                                       int(invalidate_before_ns), out.ctypes.data if out.size else None, threads)
+    if rc != 0:
+        raise RuntimeError(f"crr_load_states_verify_host failed: {rc}")
+    return out
+
+
 @dataclasses.dataclass
 class DeviceStates:
     """A StateBlobSet resident in HBM."""
@@ -462,8 +505,8 @@ class DeviceStates:
 
 class StateLoader:
     """The device loader: ``upload`` the persisted bytes, ``plan`` (decode into the scratch), then ``read`` the
-    dense image back or ``place`` it into a resumed batch's outputs.  No host fallback: a missing library or
-    device raises."""
+    dense image back, ``verify`` the stored checksums against it or ``place`` it into a resumed batch's outputs.
+    No host fallback: a missing library or device raises."""
 
     def __init__(self, engine):
         self.engine = engine
@@ -479,6 +522,8 @@ class StateLoader:
         L.crr_load_states_read.restype = ctypes.c_int
         L.crr_load_states_place.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, vp, vp]
         L.crr_load_states_place.restype = ctypes.c_int
+        L.crr_load_states_verify.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_int64, vp, vp]
+        L.crr_load_states_verify.restype = ctypes.c_int
         self.scratch = None
         self.scratch_bytes = 0
         self.summary = None
@@ -537,6 +582,24 @@ class StateLoader:
             raise RuntimeError(f"crr_load_states_read failed: {rc}")
         self.torch.cuda.synchronize(self.engine.dev)
         return buf.image(S)
+
+    def verify(self, ds: DeviceStates, stored=None, invalidate_before_ns: int = 0) -> np.ndarray:
+        """The check ``mutableStateBuilder.Load`` makes of every state of the last plan (``crr_load_states_verify``),
+        ``ds`` being the batch that plan decoded: ``abi.VERIFY_ROW`` per workflow, copied to the host.  ``stored``:
+        ``abi.STORED_CHECKSUM`` rows (``stored_checksums``); None: compute only.  Valid before or after ``read`` /
+        ``place``."""
+        from .engine import _dev_bytes
+        n = int(ds.c.n_wf)
+        st = _stored_array(stored, n)
+        d_st = _dev_bytes(self.torch, st, self.engine.dev) if st is not None else None
+        d_out = self.torch.empty(max(n, 1) * abi.VERIFY_ROW.itemsize, dtype=self.torch.uint8, device=self.engine.dev)
+        rc = self.lib.crr_load_states_verify(ctypes.byref(ds.c), ctypes.c_void_p(self.scratch.data_ptr()),
+                                             ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
+                                             ctypes.c_void_p(d_st.data_ptr() if d_st is not None else None),
+                                             int(invalidate_before_ns), ctypes.c_void_p(d_out.data_ptr()), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_states_verify failed: {rc}")
+        return d_out[:n * abi.VERIFY_ROW.itemsize].cpu().numpy().view(abi.VERIFY_ROW).copy()
 
     def place(self, db, perm: Optional[np.ndarray] = None):
         """Scatter the last plan's image into ``db``'s outputs (an ``engine.DeviceBatch``): device position p takes

@@ -93,8 +93,10 @@ enum crr_load_status {
  * bound, about 10^7 comparisons for that lane). */
 #define CRR_LOAD_MAX_BLOBS 4096
 /* Per-workflow flags.  The mutable-state checksum payload (execution/checksum.go:56-114) covers the sticky
- * task list's name and every branch's last item; the rows hold neither, so crr_checksum does not apply to a
- * workflow with one of these flags: the host verifies those. */
+ * task list's name and every branch's token and items; the rows hold neither, so crr_checksum on placed rows
+ * still does not apply to a workflow with one of these flags.  The verification Load makes of a state it has
+ * just materialised is cadence_load_verify.h: it builds the payload from the loader's scratch and the persisted
+ * bytes and covers every workflow that loaded OK, flagged or not. */
 #define CRR_LOAD_FLAG_STICKY        1u   /* StickyTaskList is non-empty */
 #define CRR_LOAD_FLAG_MULTI_BRANCH  2u   /* more than one version history; only the current one is loaded */
 

@@ -48,7 +48,8 @@ extern "C" {
  *    RefreshTasks' own task rows (task_cap), RefreshTasks' state effects without CRR_IN_EMIT_TASKS too,
  *    the fused digest (crr_inputs.digest_keys, crr_outputs.digest), crr_sizeof(13 / 14)
  * 6: the live-ID sidecar (crr_outputs.live_ids)
- * 8: the persisted mutable-state loader (cadence_load.h), crr_sizeof(15..19) */
+ * 8: the persisted mutable-state loader (cadence_load.h), crr_sizeof(15..19); added since, without a new
+ *    version: the checksum verification of loaded states (cadence_load_verify.h), crr_sizeof(20 / 21) */
 #define CRR_ABI_VERSION 8
 
 /* ---- constants restated from the reference ------------------------------------------------ */
@@ -625,7 +626,7 @@ size_t crr_sizeof(int which);   /* 0 workflow, 1 exec row, 2 activity, 3 timer, 
                                    6 vh item, 7 reset point, 8 activity side, 9 start side,
                                    10 ndc task, 11 ndc result, 12 task row, 13 crr_inputs, 14 crr_outputs,
                                    cadence_load.h: 15 state blob, 16 state wf, 17 state batch, 18 load summary,
-                                   19 load image */
+                                   19 load image, cadence_load_verify.h: 20 stored checksum, 21 verify row */
 
 /* Host-side CRC32-IEEE (hash/crc32.ChecksumIEEE) used by the shim's standalone verify. */
 uint32_t crr_crc32_ieee(const uint8_t* data, size_t len);
