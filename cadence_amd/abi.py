@@ -139,6 +139,7 @@ class Status(enum.IntEnum):
     NDC_FIRST_ITEM_MISMATCH = 22
     NDC_RETRY_TASK = 23
     NDC_BAD_INDEX = 24
+    NDC_STATE_NOT_LOADED = 25         # cadence_load_ndc.h: the task's persisted state did not load
     CAPACITY = 100
 
 
@@ -322,6 +323,26 @@ class VerifyOutcome(enum.IntEnum):
     NOT_LOADED = 6
 
 
+# ---- branch and routing decisions for tasks against loaded states (include/cadence_load_ndc.h) ----------
+REPL_TASK = np.dtype([("wf", "<u4"), ("incoming_begin", "<u4"), ("incoming_count", "<u4"), ("reserved", "<u4"),
+                      ("first_event_id", "<i8"), ("first_event_version", "<i8")])
+BRANCH_TOKEN = np.dtype([("off", "<u8"), ("len", "<u4"), ("wf", "<u4")])
+NDC_ROUTE = np.dtype([("route", "<i4"), ("status", "<i4"), ("branch", "<i4"), ("branch_is_local", "<i4"),
+                      ("last_event_id", "<i8"), ("last_version", "<i8")])
+ROUTE_NONE, ROUTE_APPLY_CURRENT, ROUTE_NON_CURRENT, ROUTE_REBUILD, ROUTE_BAD_REQUEST = range(5)
+
+
+class CLoadBranches(ctypes.Structure):
+    _fields_ = [("branches", ctypes.c_void_p), ("items", ctypes.c_void_p), ("tokens", ctypes.c_void_p),
+                ("branch_begin", ctypes.c_void_p), ("current", ctypes.c_void_p)]
+
+
+class CLoadNdcSizes(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_int32), ("n_wf", ctypes.c_uint32), ("n_tasks", ctypes.c_uint32),
+                ("n_incoming", ctypes.c_uint32), ("n_branches", ctypes.c_uint64), ("n_items", ctypes.c_uint64),
+                ("n_out_items", ctypes.c_uint64), ("work_needed", ctypes.c_uint64)]
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -389,9 +410,11 @@ def check_layout(lib):
         got = lib.crr_sizeof(i)
         if got != dt.itemsize:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {got} vs numpy {dt.itemsize}")
-    for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize)):
+    for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize),
+                 (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
-    for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage)):
+    for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage),
+                  (24, CLoadBranches), (25, CLoadNdcSizes)):
         if lib.crr_sizeof(i) != ctypes.sizeof(st):
             raise RuntimeError(f"ABI layout mismatch for {st.__name__}: C {lib.crr_sizeof(i)} vs ctypes {ctypes.sizeof(st)}")

@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "cadence_load.h"
+#include "cadence_load_ndc.h"
 #include "cadence_load_verify.h"
 #include "cadence_replay.h"
 #include "stream_device.h"
@@ -260,6 +261,11 @@ size_t crr_sizeof(int which) {
     case 19: return sizeof(crr_load_image);
     case 20: return sizeof(crr_stored_checksum);
     case 21: return sizeof(crr_verify_row);
+    case 22: return sizeof(crr_repl_task);
+    case 23: return sizeof(crr_branch_token);
+    case 24: return sizeof(crr_load_branches);
+    case 25: return sizeof(crr_load_ndc_sizes);
+    case 26: return sizeof(crr_ndc_route);
     default: return 0;
   }
 }

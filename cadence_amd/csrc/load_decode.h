@@ -13,6 +13,9 @@
 //   dict_wf      per workflow  the dictionary's key_off / key_len / bytes
 //   verify_wf    per workflow  (on request, cadence_load_verify.h) the mutable-state checksum payload's CRC from
 //                              the dense image and the persisted bytes, compared with the stored checksum
+//   branches_count_wf / branches_emit_wf   per workflow  (on request, cadence_load_ndc.h) every history of the
+//                              VersionHistories blob -> the branch table crr_ndc_prepare takes; task_row /
+//                              route_task per replication task around that call
 //
 // Wire format: thrift binary (big-endian; field header = type byte + i16 id, 0 ends a struct), field IDs of
 // .gen/go/sqlblobs/sqlblobs.go restated below (tests/golden/sqlblobs_fields.json pins them); a field whose
@@ -26,6 +29,7 @@
 #include <string.h>
 
 #include "cadence_load.h"
+#include "cadence_load_ndc.h"
 #include "cadence_load_verify.h"
 
 #if defined(__HIPCC__)
@@ -1028,6 +1032,205 @@ CRR_HD void verify_wf(const Ctx& c, uint32_t w, const uint32_t* tables, const cr
     else out.outcome = (S.value_len == 4 && S.value == out.computed) ? CRR_VERIFY_MATCH : CRR_VERIFY_MISMATCH;
   }
   result[w] = out;
+}
+
+// ---- per workflow: every branch of the VersionHistories blob (cadence_load_ndc.h) --------------------------
+// the walk's own work buffer: per-workflow counters [3][n_wf + 1] (histories and items scanned in place to
+// exclusive offsets, the longest branch as counted), the tasks' new-branch prefix [n_tasks + 1], the
+// crr_ndc_task rows built for crr_ndc_prepare, and the totals the planning call reads back
+constexpr int kBrHist = 0, kBrItems = 1, kBrLongest = 2, kBrCounters = 3;
+struct NdcLayout {
+  uint64_t cnt, out_off, rows, totals, end;
+};
+inline NdcLayout carve_ndc(uint32_t n_wf, uint32_t n_tasks) {
+  NdcLayout L;
+  uint64_t o = 0;
+  L.cnt = o;      o = align16(o + (uint64_t)kBrCounters * ((uint64_t)n_wf + 1) * sizeof(int64_t));
+  L.out_off = o;  o = align16(o + ((uint64_t)n_tasks + 1) * sizeof(int64_t));
+  L.rows = o;     o = align16(o + (uint64_t)n_tasks * sizeof(crr_ndc_task));
+  L.totals = o;   o = align16(o + 4 * sizeof(uint64_t));
+  L.end = o;
+  return L;
+}
+struct NdcWork {
+  uint8_t* s;
+  NdcLayout L;
+  uint32_t n_wf, n_tasks;
+  CRR_HD int64_t* cnt(int t) const { return reinterpret_cast<int64_t*>(s + L.cnt) + (uint64_t)t * ((uint64_t)n_wf + 1); }
+  CRR_HD int64_t* out_off() const { return reinterpret_cast<int64_t*>(s + L.out_off); }
+  CRR_HD crr_ndc_task* rows() const { return reinterpret_cast<crr_ndc_task*>(s + L.rows); }
+  CRR_HD uint64_t* totals() const { return reinterpret_cast<uint64_t*>(s + L.totals); }   // branches, items, out items
+};
+
+// Every offset used by the two branch passes was checked against its blob's end when count_wf parsed the
+// execution blob of the same `in` and walked this nested blob (so walk_vh cannot fail here on the planned
+// batch); a workflow whose recorded range does not lie within this batch's bytes, or whose walk does not give
+// the histories the plan counted (not the planned batch), has no branches, like one that did not load.
+CRR_HD bool branches_range_ok(const Ctx& c, const ExecAux& A) {
+  if (c.in.n_blobs == 0) return false;
+  const uint64_t total = c.in.blob_off[c.in.n_blobs];
+  return A.vh_len != 0 && A.vh_off <= total && A.vh_len <= total - A.vh_off;
+}
+
+// count phase: histories, items over all histories, the longest branch
+CRR_HD void branches_count_wf(const Ctx& c, const NdcWork& k, uint32_t w, Frame* stk) {
+  int64_t n_hist = 0, n_items = 0, longest = 0;
+  if (c.status()[w] == CRR_LOAD_OK) {
+    const ExecAux A = c.aux()[w];
+    if (branches_range_ok(c, A)) {
+      const Rd v = {c.in.bytes, A.vh_off, A.vh_off + A.vh_len, false};
+      VhWalk V;
+      const bool ok = walk_vh(v, -1, nullptr, V, stk, [&](uint64_t, uint32_t, uint64_t, int32_t m) {
+        ++n_hist;
+        n_items += m;
+        if (m > longest) longest = m;
+      });
+      if (!ok || V.n_hist != A.n_hist) n_hist = n_items = longest = 0;
+    }
+  }
+  k.cnt(kBrHist)[w] = n_hist;
+  k.cnt(kBrItems)[w] = n_items;
+  k.cnt(kBrLongest)[w] = longest;
+}
+
+// emit phase (after the scan of the first two counters): the branch descriptors, the tokens' positions, every
+// item, the stored current index.  Nothing is written past what the count phase counted for this workflow.
+CRR_HD void branches_emit_wf(const Ctx& c, const NdcWork& k, uint32_t w, const crr_load_branches& dst, Frame* stk) {
+  const int64_t b0 = k.cnt(kBrHist)[w], nb = k.cnt(kBrHist)[w + 1] - b0;
+  const int64_t i0 = k.cnt(kBrItems)[w], ni = k.cnt(kBrItems)[w + 1] - i0;
+  if (dst.branch_begin) {
+    dst.branch_begin[w] = b0;
+    if (w + 1 == c.in.n_wf) dst.branch_begin[w + 1] = b0 + nb;
+  }
+  if (nb == 0) {
+    if (dst.current) dst.current[w] = 0;
+    return;
+  }
+  const ExecAux A = c.aux()[w];
+  if (dst.current) dst.current[w] = A.current;
+  const Rd v = {c.in.bytes, A.vh_off, A.vh_off + A.vh_len, false};
+  VhWalk V;
+  int64_t h = 0, run = 0;
+  walk_vh(v, -1, nullptr, V, stk, [&](uint64_t tok_off, uint32_t tok_len, uint64_t items_pos, int32_t m) {
+    if (h >= nb || run + m > ni) {   // not the bytes the plan counted
+      h = nb;
+      return;
+    }
+    if (dst.branches) {
+      const crr_ndc_branch br = {(uint32_t)(i0 + run), (uint32_t)m};
+      dst.branches[b0 + h] = br;
+    }
+    if (dst.tokens) {
+      const crr_branch_token tk = {tok_len ? tok_off : 0, tok_len, w};
+      dst.tokens[b0 + h] = tk;
+    }
+    if (dst.items) {
+      Rd it = {v.p, items_pos, v.end, false};
+      for (int32_t q = 0; q < m; ++q) dst.items[i0 + run + q] = read_vh_item(it, stk);
+    }
+    run += m;
+    ++h;
+  });
+}
+
+// the new-branch room of task k: the longest local branch of its workflow (0: not decided)
+CRR_HD int64_t task_room(const NdcWork& k, const crr_repl_task& t) {
+  return t.wf < k.n_wf ? k.cnt(kBrLongest)[t.wf] : 0;
+}
+
+// whether task `t` is decided, and if not the status it carries
+CRR_HD int32_t task_refusal(const NdcWork& k, const crr_repl_task& t, uint32_t n_incoming) {
+  if (t.wf >= k.n_wf || k.cnt(kBrHist)[t.wf + 1] == k.cnt(kBrHist)[t.wf]) return CRR_ERR_NDC_STATE_NOT_LOADED;
+  if (t.incoming_begin > n_incoming || t.incoming_count > n_incoming - t.incoming_begin) return CRR_ERR_NDC_BAD_INDEX;
+  return CRR_OK;
+}
+
+// the crr_ndc_task row of task `t` (after both scans): the workflow's branches and stored current index, the
+// incoming items where the run call copies them (behind the n_items local ones), its room in out_items
+CRR_HD crr_ndc_task task_row(const NdcWork& k, const crr_repl_task& t, uint32_t idx, uint32_t n_incoming,
+                             uint64_t n_items, const int32_t* current) {
+  crr_ndc_task r;
+  memset(&r, 0, sizeof r);
+  r.out_begin = (uint32_t)k.out_off()[idx];
+  r.first_event_id = t.first_event_id;
+  r.first_event_version = t.first_event_version;
+  if (task_refusal(k, t, n_incoming) != CRR_OK) return r;   // no branches: crr_ndc_prepare reads nothing for it
+  r.branch_begin = (uint32_t)k.cnt(kBrHist)[t.wf];
+  r.branch_count = (uint32_t)(k.cnt(kBrHist)[t.wf + 1] - k.cnt(kBrHist)[t.wf]);
+  r.current_index = current[t.wf];
+  r.incoming_begin = (uint32_t)(n_items + t.incoming_begin);
+  r.incoming_count = t.incoming_count;
+  return r;
+}
+
+// conflictResolverImpl.prepareMutableState (ndc/conflict_resolver.go:75-120) for task `idx`, over the histories
+// as prepareVersionHistory left them: `res` is crr_ndc_prepare's row (rewritten here for a task that was not
+// decided), `row` the task's crr_ndc_task
+CRR_HD void route_task(const NdcWork& k, const crr_repl_task& t, uint32_t idx, uint32_t n_incoming,
+                       const crr_ndc_branch* branches, const crr_vh_item* items, const crr_vh_item* out_items,
+                       crr_ndc_result* results, crr_ndc_route* routes) {
+  crr_ndc_route o;
+  memset(&o, 0, sizeof o);
+  o.route = CRR_ROUTE_NONE;
+  const int32_t refusal = task_refusal(k, t, n_incoming);
+  if (refusal != CRR_OK) {
+    crr_ndc_result z;
+    memset(&z, 0, sizeof z);
+    z.status = refusal;
+    z.action = CRR_NDC_DUPLICATE;
+    results[idx] = z;
+    o.status = refusal;
+    routes[idx] = o;
+    return;
+  }
+  const crr_ndc_result r = results[idx];
+  const crr_ndc_task row = k.rows()[idx];
+  o.status = r.status;
+  if (r.status != CRR_OK || r.action == CRR_NDC_DUPLICATE) {
+    routes[idx] = o;
+    return;
+  }
+  if (r.branch_index == r.new_current_index) {   // :88-90
+    o.route = CRR_ROUTE_APPLY_CURRENT;
+    routes[idx] = o;
+    return;
+  }
+  // a branch's last item (GetLastItem): local branches from the table, the new one from the task's out_items run
+  auto last_item = [&](int32_t b, crr_vh_item& it) {
+    if (b >= 0 && (uint32_t)b < row.branch_count) {
+      const crr_ndc_branch br = branches[row.branch_begin + (uint32_t)b];
+      if (br.item_count == 0) return false;
+      it = items[br.item_begin + br.item_count - 1];
+      return true;
+    }
+    if (b != (int32_t)row.branch_count || r.action != CRR_NDC_NEW_BRANCH || r.new_item_count <= 0) return false;
+    it = out_items[row.out_begin + (uint32_t)r.new_item_count - 1];
+    return true;
+  };
+  crr_vh_item cur_last = {0, 0};
+  if (!last_item(r.new_current_index, cur_last)) {   // :92-99
+    o.status = CRR_ERR_VH_EMPTY;
+    routes[idx] = o;
+    return;
+  }
+  const int64_t version = t.first_event_version;
+  if (version < cur_last.version) {
+    o.route = CRR_ROUTE_NON_CURRENT;                 // :102-104
+  } else if (version == cur_last.version) {
+    o.route = CRR_ROUTE_BAD_REQUEST;                 // :106-110
+  } else {                                           // :112-119 -> rebuild (:122-158)
+    crr_vh_item last = {0, 0};
+    if (!last_item(r.branch_index, last)) {
+      o.status = CRR_ERR_VH_EMPTY;
+    } else {
+      o.route = CRR_ROUTE_REBUILD;
+      o.branch = r.branch_index;
+      o.branch_is_local = (uint32_t)r.branch_index < row.branch_count ? 1 : 0;
+      o.last_event_id = last.event_id;
+      o.last_version = last.version;
+    }
+  }
+  routes[idx] = o;
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

@@ -11,6 +11,11 @@
 //   load_place_kernel   one lane per device position: the dense rows scattered into a replay's slot tables
 //   load_verify_kernel  one lane per workflow: the mutable-state checksum payload generated from the dense image
 //                       and the persisted bytes, its CRC compared with the stored checksum (cadence_load_verify.h)
+//   load_branches_count_kernel / load_branches_emit_kernel   one lane per workflow: every history of the nested
+//                       VersionHistories blob counted, then written as the branch table crr_ndc_prepare takes
+//                       (cadence_load_ndc.h); load_ndc_scan_kernel between them, load_scan_kernel's pattern
+//   load_task_room_kernel / load_task_rows_kernel / load_route_kernel   one lane per replication task: its room for
+//                       new-branch items, its crr_ndc_task row, and after crr_ndc_prepare the routing decision
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -173,6 +178,73 @@ __global__ void __launch_bounds__(kBlock) load_verify_kernel(Ctx c, const crr_st
   if (w < c.in.n_wf) verify_wf(c, w, crc_tables, stored, invalidate_before_ns, result, stk[threadIdx.x]);
 }
 
+// ---- cadence_load_ndc.h: every branch of every loaded state, the tasks' rows, the routing decision ------------
+__global__ void __launch_bounds__(kBlock) load_branches_count_kernel(Ctx c, NdcWork k) {
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  const uint32_t w = blockIdx.x * kBlock + threadIdx.x;
+  if (w < c.in.n_wf) branches_count_wf(c, k, w, stk[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kBlock) load_branches_emit_kernel(Ctx c, NdcWork k, crr_load_branches dst) {
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  const uint32_t w = blockIdx.x * kBlock + threadIdx.x;
+  if (w < c.in.n_wf) branches_emit_wf(c, k, w, dst, stk[threadIdx.x]);
+}
+
+// load_scan_kernel's pattern over plain rows: `rows` arrays of n + 1 int64 each, scanned in place to exclusive
+// prefixes ([n] = the total, which also goes to totals[row])
+__global__ void __launch_bounds__(kScanBlock) load_ndc_scan_kernel(int64_t* base, uint32_t n, int rows, uint64_t* totals) {
+  __shared__ int64_t part[kScanBlock];
+  const uint32_t per = (n + kScanBlock - 1) / kScanBlock;
+  for (int t = 0; t < rows; ++t) {
+    int64_t* p = base + (uint64_t)t * ((uint64_t)n + 1);
+    const uint32_t lo = min((uint64_t)threadIdx.x * per, (uint64_t)n), hi = min((uint64_t)lo + per, (uint64_t)n);
+    int64_t s = 0;
+    for (uint32_t i = lo; i < hi; ++i) s += p[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < kScanBlock; d <<= 1) {
+      const int64_t o = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
+      __syncthreads();
+      part[threadIdx.x] += o;
+      __syncthreads();
+    }
+    int64_t run = part[threadIdx.x] - s;
+    for (uint32_t i = lo; i < hi; ++i) {
+      const int64_t x = p[i];
+      p[i] = run;
+      run += x;
+    }
+    if (threadIdx.x == kScanBlock - 1) {
+      p[n] = part[kScanBlock - 1];
+      totals[t] = (uint64_t)part[kScanBlock - 1];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) load_task_room_kernel(NdcWork k, const crr_repl_task* tasks) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < k.n_tasks) k.out_off()[i] = task_room(k, tasks[i]);
+}
+
+__global__ void __launch_bounds__(kBlock) load_task_rows_kernel(NdcWork k, const crr_repl_task* tasks, uint32_t n_incoming,
+                                                                uint64_t n_items, const int32_t* current, uint32_t* out_begin) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= k.n_tasks) return;
+  const crr_ndc_task r = task_row(k, tasks[i], i, n_incoming, n_items, current);
+  k.rows()[i] = r;
+  if (out_begin) out_begin[i] = r.out_begin;
+}
+
+__global__ void __launch_bounds__(kBlock) load_route_kernel(NdcWork k, const crr_repl_task* tasks, uint32_t n_incoming,
+                                                            const crr_ndc_branch* branches, const crr_vh_item* items,
+                                                            const crr_vh_item* out_items, crr_ndc_result* results,
+                                                            crr_ndc_route* routes) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < k.n_tasks) route_task(k, tasks[i], i, n_incoming, branches, items, out_items, results, routes);
+}
+
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
 
 constexpr uint32_t kScanA = 0xFFFu & ~((1u << CRR_LOAD_T_KEYS) | (1u << CRR_LOAD_T_KEY_BYTES));
@@ -322,6 +394,116 @@ int crr_load_states_verify(const crr_state_batch* in, const void* scratch, size_
   if (in->n_wf == 0) return 0;
   c.in = *in;
   hipLaunchKernelGGL(load_verify_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c, stored, invalidate_before_ns, result);
+  return (int)hipGetLastError();
+}
+
+size_t crr_load_ndc_scratch_bytes(uint32_t n_wf, uint32_t n_tasks) { return (size_t)carve_ndc(n_wf, n_tasks).end; }
+
+// the loader's context for the branch walk (a batch without workflows has no plan to read) and the work buffer
+static bool ndc_usable(const crr_state_batch* in, const void* scratch, size_t scratch_bytes, const crr_load_summary* S,
+                       void* work, uint32_t n_tasks, Ctx& c, NdcWork& k) {
+  if (!in || !S || !work || ((uintptr_t)work & 15u)) return false;
+  if (in->n_blobs != S->n_blobs || in->n_wf != S->n_wf) return false;   // not the planned batch
+  if (in->n_wf) {
+    if (!plan_usable(scratch, scratch_bytes, S, c)) return false;
+    if (in->n_blobs && (!in->bytes || !in->blob_off)) return false;
+  } else {
+    memset(&c, 0, sizeof c);
+  }
+  c.in = *in;
+  k.s = static_cast<uint8_t*>(work);
+  k.L = carve_ndc(in->n_wf, n_tasks);
+  k.n_wf = in->n_wf;
+  k.n_tasks = n_tasks;
+  return true;
+}
+
+int crr_load_ndc_plan(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                      const crr_load_summary* summary_host, const crr_repl_task* tasks, uint32_t n_tasks,
+                      uint32_t n_incoming, void* work, size_t work_bytes, crr_load_ndc_sizes* plan, void* stream) {
+  Ctx c;
+  NdcWork k;
+  if (!plan || (n_tasks && !tasks) || !ndc_usable(in, scratch, scratch_bytes, summary_host, work, n_tasks, c, k)) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  memset(plan, 0, sizeof *plan);
+  plan->n_wf = in->n_wf;
+  plan->n_tasks = n_tasks;
+  plan->n_incoming = n_incoming;
+  plan->work_needed = k.L.end;
+  if (k.L.end > work_bytes) {
+    plan->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    return 0;
+  }
+  hipError_t e;
+  if ((e = hipMemsetAsync(k.totals(), 0, 4 * sizeof(uint64_t), s)) != hipSuccess) return (int)e;
+  if (in->n_wf) {
+    hipLaunchKernelGGL(load_branches_count_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c, k);
+    hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, k.cnt(0), in->n_wf, 2, k.totals());
+  } else if ((e = hipMemsetAsync(k.cnt(0), 0, kBrCounters * sizeof(int64_t), s)) != hipSuccess) {
+    return (int)e;
+  }
+  if (n_tasks) {
+    hipLaunchKernelGGL(load_task_room_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, k, tasks);
+    hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, k.out_off(), n_tasks, 1, k.totals() + 2);
+  } else if ((e = hipMemsetAsync(k.out_off(), 0, sizeof(int64_t), s)) != hipSuccess) {
+    return (int)e;
+  }
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[4];
+  if ((e = hipMemcpyAsync(h, k.totals(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  plan->n_branches = h[0];
+  plan->n_items = h[1];
+  plan->n_out_items = h[2];
+  // crr_ndc_branch / crr_ndc_task index with 32 bits
+  if (h[0] > 0xFFFFFFFFull || h[1] + n_incoming > 0xFFFFFFFFull || h[2] > 0xFFFFFFFFull) return -1;
+  return 0;
+}
+
+int crr_load_ndc_run(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                     const crr_load_summary* summary_host, const crr_repl_task* tasks, const crr_vh_item* incoming,
+                     void* work, size_t work_bytes, const crr_load_ndc_sizes* plan_host, const crr_load_branches* dst,
+                     crr_ndc_result* results, crr_ndc_route* routes, crr_vh_item* out_items, uint32_t* out_begin,
+                     void* stream) {
+  Ctx c;
+  NdcWork k;
+  if (!plan_host || plan_host->err != 0 || !dst || !dst->branch_begin) return -1;
+  const crr_load_ndc_sizes& P = *plan_host;
+  if (!ndc_usable(in, scratch, scratch_bytes, summary_host, work, P.n_tasks, c, k)) return -1;
+  if (P.n_wf != in->n_wf || P.work_needed != k.L.end || k.L.end > work_bytes) return -1;
+  if (P.n_branches > 0xFFFFFFFFull || P.n_items + P.n_incoming > 0xFFFFFFFFull || P.n_out_items > 0xFFFFFFFFull) return -1;
+  if (in->n_wf && !dst->current) return -1;
+  if (P.n_branches && (!dst->branches || !dst->tokens)) return -1;
+  if ((P.n_items || (P.n_tasks && P.n_incoming)) && !dst->items) return -1;
+  if (P.n_tasks && (!tasks || !results || !routes || !out_items || !dst->branches || !dst->items || !dst->current)) return -1;
+  if (P.n_tasks && P.n_incoming && !incoming) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  hipError_t e;
+  if (in->n_wf) hipLaunchKernelGGL(load_branches_emit_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c, k, *dst);
+  else if ((e = hipMemsetAsync(dst->branch_begin, 0, sizeof(int64_t), s)) != hipSuccess) return (int)e;
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  if (P.n_tasks == 0) return 0;
+  // the incoming items behind the local ones: one items array for crr_ndc_prepare
+  if (P.n_incoming && (e = hipMemcpyAsync(dst->items + P.n_items, incoming, (size_t)P.n_incoming * sizeof(crr_vh_item),
+                                          hipMemcpyDeviceToDevice, s)) != hipSuccess)
+    return (int)e;
+  hipLaunchKernelGGL(load_task_rows_kernel, grid_of(P.n_tasks), dim3(kBlock), 0, s, k, tasks, P.n_incoming, P.n_items,
+                     dst->current, out_begin);
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  crr_ndc_inputs ni;
+  ni.tasks = k.rows();
+  ni.branches = dst->branches;
+  ni.items = dst->items;
+  ni.n_tasks = P.n_tasks;
+  ni.reserved = 0;
+  const int rc = crr_ndc_prepare(&ni, results, out_items, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(load_route_kernel, grid_of(P.n_tasks), dim3(kBlock), 0, s, k, tasks, P.n_incoming, dst->branches,
+                     dst->items, out_items, results, routes);
   return (int)hipGetLastError();
 }
 

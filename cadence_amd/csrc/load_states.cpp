@@ -2,7 +2,8 @@
 // (include/cadence_load.h).  The decoder itself is load_decode.h, the same text the gfx950 kernels of
 // load_kernel.hip compile; this file runs its phases as loops (optionally over threads), with serial
 // prefix scans between them, over a scratch laid out exactly like the device's.
-// crr_load_states_verify_host (include/cadence_load_verify.h) runs the same load, then load_decode.h's verify_wf.
+// crr_load_states_verify_host (include/cadence_load_verify.h) runs the same load, then load_decode.h's verify_wf;
+// crr_load_branches_host (include/cadence_load_ndc.h) the same load, then its branch walk.
 #include <stdlib.h>
 
 #include <thread>
@@ -113,6 +114,49 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
     if (dst->status) memcpy(dst->status, c.status(), n * sizeof(int32_t));
     if (dst->flags) memcpy(dst->flags, c.flags(), n * sizeof(uint32_t));
   }
+  free(c.s);
+  return 0;
+}
+
+// the branch table of every loaded state (include/cadence_load_ndc.h): load_decode.h's count and emit phases as
+// host loops over a work buffer laid out like the device's, a serial scan between them
+extern "C" int crr_load_branches_host(const crr_state_batch* in, const crr_load_branches* dst, crr_load_ndc_sizes* plan,
+                                      int threads) {
+  if (!in || !plan) return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
+  NdcWork k;
+  k.L = carve_ndc(n_wf, 0);
+  k.n_wf = n_wf;
+  k.n_tasks = 0;
+  k.s = static_cast<uint8_t*>(calloc(k.L.end + 16, 1));
+  if (!k.s) {
+    free(c.s);
+    return -2;
+  }
+  parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_count_wf(c, k, w, stk); });
+  for (int t = 0; t < 2; ++t) {
+    int64_t* p = k.cnt(t);
+    int64_t run = 0;
+    for (uint32_t w = 0; w < n_wf; ++w) {
+      const int64_t x = p[w];
+      p[w] = run;
+      run += x;
+    }
+    p[n_wf] = run;
+  }
+  memset(plan, 0, sizeof *plan);
+  plan->n_wf = n_wf;
+  plan->n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
+  plan->n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
+  plan->work_needed = k.L.end;
+  if (dst) {
+    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, *dst, stk); });
+    if (n_wf == 0 && dst->branch_begin) dst->branch_begin[0] = 0;
+  }
+  free(k.s);
   free(c.s);
   return 0;
 }

@@ -16,6 +16,11 @@ blobs; it is the reference encoder for a cgo shim's tests.
 ``StateLoader.verify`` / ``load_states_verify_host`` make the check ``mutableStateBuilder.Load`` makes right
 after materialising a state -- the stored ``checksum.Checksum`` against a freshly generated payload
 (``include/cadence_load_verify.h``) -- for every state that loaded OK, sticky and multi-branch ones included.
+
+``StateLoader.branches`` / ``load_branches_host`` give every branch of every loaded state, and
+``StateLoader.ndc_prepare`` decides and routes replication tasks against those states on the device
+(``include/cadence_load_ndc.h``): ``prepareVersionHistory`` through ``crr_ndc_prepare``, then
+``prepareMutableState``'s route per task; ``apply_mask`` turns the routes into the workflows to resume.
 """
 from __future__ import annotations
 
@@ -123,17 +128,20 @@ def to_unix_nano(t: int) -> int:
 
 
 def encode_version_histories(current: int, histories: Sequence) -> bytes:
-    """shared.VersionHistories as a thriftrw DataBlob: ``histories`` = [(branch token, [(event id, version)])]."""
+    """shared.VersionHistories as a thriftrw DataBlob: ``histories`` = [(branch token, [(event id, version)])];
+    a token or an items list that is None is left out of its VersionHistory struct."""
     w = W()
     w.b += b"\x59"
     w.i32(10, current)
     w.field(T_LIST, 20)
     w.b += bytes([T_STRUCT]) + struct.pack(">i", len(histories))
     for token, items in histories:
-        w.string(10, token)
-        w.field(T_LIST, 20)
-        w.b += bytes([T_STRUCT]) + struct.pack(">i", len(items))
-        for eid, ver in items:
+        if token is not None:
+            w.string(10, token)
+        if items is not None:
+            w.field(T_LIST, 20)
+            w.b += bytes([T_STRUCT]) + struct.pack(">i", len(items))
+        for eid, ver in items or ():
             w.i64(10, eid)
             w.i64(20, ver)
             w.b += b"\x00"
@@ -212,9 +220,12 @@ def _inverse(interner: Optional[Dict[str, int]]) -> Dict[int, str]:
     return {v: k for k, v in (interner or {"": 0}).items()}
 
 
-def execution_values(ex, token: bytes, vh_items, points, sticky: str = "", decoy_branch: bool = False) -> Dict[str, object]:
+def execution_values(ex, token: bytes, vh_items, points, sticky: str = "", decoy_branch: bool = False,
+                     branches=None) -> Dict[str, object]:
     """Field values of the execution blob for exec row ``ex`` (workflowExecutionInfoToThrift: every pointer
-    field set; the nil-able ones the replay path leaves nil are omitted)."""
+    field set; the nil-able ones the replay path leaves nil are omitted).  ``branches``: ``(histories, current
+    index)`` written instead of the one branch ``(token, vh_items)`` -- ``histories`` a list of ``(token, items)``
+    as ``encode_version_histories`` takes them, an entry that is None standing for ``(token, vh_items)``."""
     src = int(ex["decision_request_src"])
     request_id = "emptyUuid" if src == abi.SRC_EMPTY_UUID else ("" if src == abi.SRC_NONE else det_uuid("decision", src))
     histories = [(token, vh_items)]
@@ -222,6 +233,9 @@ def execution_values(ex, token: bytes, vh_items, points, sticky: str = "", decoy
     if decoy_branch:   # a second, non-current branch in front of the current one
         histories = [(b"decoy-branch-token", [(1, 0), (7, 3)])] + histories
         current = 1
+    if branches is not None:
+        histories = [(token, vh_items) if h is None else h for h in branches[0]]
+        current = int(branches[1])
     v = {
         "ParentWorkflowID": "", "InitiatedID": abi.EMPTY_EVENT_ID, "CompletionEventEncoding": "",
         "TaskList": "task-list", "WorkflowTypeName": "workflow-type", "WorkflowTimeoutSeconds": 3600,
@@ -297,15 +311,21 @@ def initiated_values(r, signal: bool) -> Dict[str, object]:
 
 
 def encode_states(batch: HistoryBatch, result: ReplayResult, histories: Sequence[WorkflowHistory],
-                  shuffle_seed: Optional[int] = None, sticky: Iterable[int] = (), multi_branch: Iterable[int] = ()
-                  ) -> StateBlobSet:
+                  shuffle_seed: Optional[int] = None, sticky: Iterable[int] = (), multi_branch: Iterable[int] = (),
+                  branches=None) -> StateBlobSet:
     """The persisted form of the states ``result`` holds for ``batch`` (a replay of ``histories``), canonical
     workflow order: what the SQL store would return for each execution whose replay ended OK (any other
     workflow has no blobs).  The execution blob comes first, then activities, timers, children,
     request-cancels and signals in row order; ``shuffle_seed`` shuffles each execution's blobs.
-    ``sticky`` / ``multi_branch``: workflow indices given a sticky task list / a second, non-current branch."""
+    ``sticky`` / ``multi_branch``: workflow indices given a sticky task list / a second, non-current branch.
+    ``branches``: ``{workflow index: (histories, current index)}`` (or a sequence indexed by workflow, None: as
+    without it) -- the branch set written for that workflow, as ``execution_values`` takes it."""
     loaded = result.to_loaded(batch)
     sticky, multi_branch = set(sticky), set(multi_branch)
+    if branches is None:
+        branches = {}
+    elif not isinstance(branches, dict):
+        branches = {w: b for w, b in enumerate(branches) if b is not None}
     rng = random.Random(shuffle_seed) if shuffle_seed is not None else None
     offs = {name: np.cumsum(loaded.counts(name)) - loaded.counts(name) for name in loaded.rows}
     workflows = []
@@ -325,7 +345,7 @@ def encode_states(batch: HistoryBatch, result: ReplayResult, histories: Sequence
         items = [(int(r["event_id"]), int(r["version"])) for r in rows("vh", "n_vh_items")]
         points = [(names[int(r["key"])], bool(int(r["flags"]) & abi.ROW_RESETTABLE)) for r in rows("rp", "n_reset_points")]
         blobs = [(abi.STATE_EXECUTION, 0, 0, "", encode_struct("WorkflowExecutionInfo", execution_values(
-            ex, token, items, points, "sticky-tl" if w in sticky else "", w in multi_branch)))]
+            ex, token, items, points, "sticky-tl" if w in sticky else "", w in multi_branch, branches.get(w))))]
         for r in rows("act", "n_activity"):
             blobs.append((abi.STATE_ACTIVITY, int(r["schedule_id"]), to_unix_nano(r["last_heartbeat_time"]), "",
                           encode_struct("ActivityInfo", activity_values(r, names[int(r["key"])]))))
@@ -439,6 +459,8 @@ def _host_lib():
         L.crr_load_states_host.restype = ctypes.c_int
         L.crr_load_states_verify_host.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int]
         L.crr_load_states_verify_host.restype = ctypes.c_int
+        L.crr_load_branches_host.argtypes = [vp, vp, vp, ctypes.c_int]
+        L.crr_load_branches_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -495,6 +517,86 @@ def load_states_verify_host(sbs: StateBlobSet, stored=None, invalidate_before_ns
     return out
 
 
+# ---- every branch of the loaded states; tasks decided and routed against them (include/cadence_load_ndc.h) -----
+@dataclasses.dataclass
+class Branches:
+    """Host image of ``crr_load_branches``: workflow w's histories in stored order are
+    ``branches[branch_begin[w]:branch_begin[w + 1]]`` (items ``items[item_begin:item_begin + item_count]``), their
+    tokens at the same indices as ranges of the blob set's bytes; a workflow that did not load has none."""
+    branches: np.ndarray      # abi.NDC_BRANCH
+    items: np.ndarray         # abi.VH_ITEM (the local items only)
+    tokens: np.ndarray        # abi.BRANCH_TOKEN
+    branch_begin: np.ndarray  # int64 [n_wf + 1]
+    current: np.ndarray       # int32 [n_wf]
+
+    def of(self, w: int):
+        """[(item list, token range)] of workflow w."""
+        out = []
+        for b in range(int(self.branch_begin[w]), int(self.branch_begin[w + 1])):
+            o, n = int(self.branches[b]["item_begin"]), int(self.branches[b]["item_count"])
+            out.append(([(int(x["event_id"]), int(x["version"])) for x in self.items[o:o + n]],
+                        (int(self.tokens[b]["off"]), int(self.tokens[b]["len"]))))
+        return out
+
+    def image_bytes(self) -> Dict[str, bytes]:
+        return {f: getattr(self, f).tobytes() for f in ("branches", "items", "tokens", "branch_begin", "current")}
+
+
+def load_branches_host(sbs: StateBlobSet, threads: int = 1) -> Branches:
+    """The branch table by the host restatement (``crr_load_branches_host``)."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    P = abi.CLoadNdcSizes()
+    rc = L.crr_load_branches_host(ctypes.byref(c), None, ctypes.byref(P), threads)   # sizes
+    if rc != 0:
+        raise RuntimeError(f"crr_load_branches_host failed: {rc}")
+    out = Branches(np.zeros(int(P.n_branches), abi.NDC_BRANCH), np.zeros(int(P.n_items), abi.VH_ITEM),
+                   np.zeros(int(P.n_branches), abi.BRANCH_TOKEN), np.zeros(int(P.n_wf) + 1, np.int64),
+                   np.zeros(int(P.n_wf), np.int32))
+    d = abi.CLoadBranches()
+    for f in ("branches", "items", "tokens", "branch_begin", "current"):
+        a = getattr(out, f)
+        setattr(d, f, a.ctypes.data if a.size else None)
+    rc = L.crr_load_branches_host(ctypes.byref(c), ctypes.byref(d), ctypes.byref(P), threads)
+    if rc != 0:
+        raise RuntimeError(f"crr_load_branches_host failed: {rc}")
+    return out
+
+
+def apply_mask(routes: np.ndarray, tasks: Optional[np.ndarray] = None, n_wf: Optional[int] = None) -> np.ndarray:
+    """The workflows whose task is to be replayed onto the placed rows (``ROUTE_APPLY_CURRENT``), as
+    ``LoadedImage.resumable(mask=...)`` takes them (canonical workflow order; ``replication.BlobReplication``'s
+    ``split`` is the same mask at the device positions, ``mask[batch.perm]``).  ``tasks`` (``abi.REPL_TASK``) names
+    each route's workflow; without it route k belongs to workflow k."""
+    apply = np.asarray(routes["route"]) == abi.ROUTE_APPLY_CURRENT
+    if tasks is None:
+        return apply if n_wf is None else np.concatenate([apply, np.zeros(max(n_wf - apply.size, 0), bool)])[:n_wf]
+    wf = np.asarray(tasks["wf"], np.int64)
+    n = int(n_wf if n_wf is not None else (wf.max() + 1 if wf.size else 0))
+    mask = np.zeros(n, bool)
+    ok = apply & (wf < n)
+    mask[wf[ok]] = True
+    return mask
+
+
+@dataclasses.dataclass
+class DeviceBranches:
+    """The branch table resident in HBM (``crr_load_branches``); ``items`` holds the local items, then the incoming
+    items of the tasks it was built with."""
+    plan: abi.CLoadNdcSizes
+    tensors: Dict[str, object]
+    c: abi.CLoadBranches
+
+    def read(self) -> Branches:
+        P = self.plan
+
+        def host(f, dt, n):
+            return self.tensors[f][:n * np.dtype(dt).itemsize].cpu().numpy().view(dt).copy()
+        return Branches(host("branches", abi.NDC_BRANCH, int(P.n_branches)), host("items", abi.VH_ITEM, int(P.n_items)),
+                        host("tokens", abi.BRANCH_TOKEN, int(P.n_branches)), host("branch_begin", np.int64, int(P.n_wf) + 1),
+                        host("current", np.int32, int(P.n_wf)))
+
+
 @dataclasses.dataclass
 class DeviceStates:
     """A StateBlobSet resident in HBM."""
@@ -524,6 +626,12 @@ class StateLoader:
         L.crr_load_states_place.restype = ctypes.c_int
         L.crr_load_states_verify.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_int64, vp, vp]
         L.crr_load_states_verify.restype = ctypes.c_int
+        L.crr_load_ndc_scratch_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.crr_load_ndc_scratch_bytes.restype = ctypes.c_size_t
+        L.crr_load_ndc_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_size_t, vp, vp]
+        L.crr_load_ndc_plan.restype = ctypes.c_int
+        L.crr_load_ndc_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+        L.crr_load_ndc_run.restype = ctypes.c_int
         self.scratch = None
         self.scratch_bytes = 0
         self.summary = None
@@ -615,3 +723,75 @@ class StateLoader:
                                             ctypes.byref(db.c_out), self._stream())
         if rc != 0:
             raise RuntimeError(f"crr_load_states_place failed: {rc}")
+
+    # ---- include/cadence_load_ndc.h ------------------------------------------------------------------------
+    def _ndc(self, ds: DeviceStates, tasks, incoming_items):
+        """Plan (one synchronisation) and enqueue the branch table of the last plan's states and, with tasks, their
+        decisions and routes: (DeviceBranches, device tensors of results / routes / out_items / out_begin)."""
+        from .engine import _dev_bytes
+        torch, dev = self.torch, self.engine.dev
+        tasks = np.zeros(0, abi.REPL_TASK) if tasks is None else np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
+        inc = np.zeros(0, abi.VH_ITEM) if incoming_items is None else np.ascontiguousarray(incoming_items, dtype=abi.VH_ITEM)
+        n_tasks, n_inc = int(tasks.shape[0]), int(inc.shape[0])
+        d_tasks = _dev_bytes(torch, tasks, dev) if n_tasks else None
+        d_inc = _dev_bytes(torch, inc, dev) if n_inc else None
+        return self._ndc_device(ds, d_tasks, n_tasks, d_inc, n_inc)
+
+    def _ndc_device(self, ds: DeviceStates, d_tasks, n_tasks: int, d_inc, n_inc: int):
+        """``_ndc`` on tasks and incoming items already resident (device byte tensors; None: none)."""
+        torch, dev, n_wf = self.torch, self.engine.dev, int(ds.c.n_wf)
+        work_bytes = int(self.lib.crr_load_ndc_scratch_bytes(n_wf, n_tasks))
+        work = torch.empty(work_bytes + 16, dtype=torch.uint8, device=dev)
+        scratch = ctypes.c_void_p(self.scratch.data_ptr() if self.scratch is not None else None)
+        P = abi.CLoadNdcSizes()
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+        rc = self.lib.crr_load_ndc_plan(ctypes.byref(ds.c), scratch, ctypes.c_size_t(self.scratch_bytes),
+                                        ctypes.byref(self.summary), ptr(d_tasks), n_tasks, n_inc, ptr(work),
+                                        ctypes.c_size_t(work_bytes), ctypes.byref(P), self._stream())
+        if rc != 0 or P.err != 0:
+            raise RuntimeError(f"crr_load_ndc_plan failed: {rc} (err {P.err})")
+
+        def buf(n, dt, fill=False):   # every buffer is written in full by the call, but for the new-branch items' room
+            return (torch.zeros if fill else torch.empty)(max(n, 1) * np.dtype(dt).itemsize, dtype=torch.uint8, device=dev)
+        T = {"branches": buf(int(P.n_branches), abi.NDC_BRANCH), "items": buf(int(P.n_items) + n_inc, abi.VH_ITEM),
+             "tokens": buf(int(P.n_branches), abi.BRANCH_TOKEN), "branch_begin": buf(n_wf + 1, np.int64),
+             "current": buf(n_wf, np.int32)}
+        d = abi.CLoadBranches()
+        for f, t in T.items():
+            setattr(d, f, t.data_ptr())
+        out = {"results": buf(n_tasks, abi.NDC_RESULT), "routes": buf(n_tasks, abi.NDC_ROUTE),
+               "out_items": buf(int(P.n_out_items), abi.VH_ITEM, True), "out_begin": buf(n_tasks, np.uint32)}
+        rc = self.lib.crr_load_ndc_run(ctypes.byref(ds.c), scratch, ctypes.c_size_t(self.scratch_bytes),
+                                       ctypes.byref(self.summary), ptr(d_tasks), ptr(d_inc), ptr(work),
+                                       ctypes.c_size_t(work_bytes), ctypes.byref(P), ctypes.byref(d), ptr(out["results"]),
+                                       ptr(out["routes"]), ptr(out["out_items"]), ptr(out["out_begin"]), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_ndc_run failed: {rc}")
+        T["work"], T["tasks"], T["incoming"] = work, d_tasks, d_inc   # alive until the stream has run them
+        return DeviceBranches(P, T, d), out
+
+    def branches(self, ds: DeviceStates) -> DeviceBranches:
+        """Every branch of every state of the last plan (``ds`` the batch it decoded), left on the device."""
+        return self._ndc(ds, None, None)[0]
+
+    def ndc_prepare(self, ds: DeviceStates, tasks, incoming_items, on_device: bool = False):
+        """``prepareVersionHistory`` and ``prepareMutableState`` for replication ``tasks`` (``abi.REPL_TASK``, their
+        incoming VersionHistoryItems in ``incoming_items``, ``abi.VH_ITEM``) against the states of the last plan:
+        ``(results abi.NDC_RESULT[n], routes abi.NDC_ROUTE[n], out_items abi.VH_ITEM[])`` -- task k's new-branch
+        items are ``out_items[out_begin[k]:][:results[k]["new_item_count"]]``, ``out_begin`` the exclusive prefix
+        over the tasks of the longest local branch of each task's workflow (``self.last_ndc`` keeps it, the
+        ``DeviceBranches`` and the device tensors).  ``on_device``: the three as device byte tensors, nothing
+        copied back."""
+        br, out = self._ndc(ds, tasks, incoming_items)
+        self.last_ndc = (br, out)
+        if on_device:
+            return out["results"], out["routes"], out["out_items"]
+        n = int(br.plan.n_tasks)
+
+        def host(f, dt, k):
+            return out[f][:k * np.dtype(dt).itemsize].cpu().numpy().view(dt).copy()
+        self.last_out_begin = host("out_begin", np.uint32, n)
+        return (host("results", abi.NDC_RESULT, n), host("routes", abi.NDC_ROUTE, n),
+                host("out_items", abi.VH_ITEM, int(br.plan.n_out_items)))

@@ -49,7 +49,9 @@ extern "C" {
  *    the fused digest (crr_inputs.digest_keys, crr_outputs.digest), crr_sizeof(13 / 14)
  * 6: the live-ID sidecar (crr_outputs.live_ids)
  * 8: the persisted mutable-state loader (cadence_load.h), crr_sizeof(15..19); added since, without a new
- *    version: the checksum verification of loaded states (cadence_load_verify.h), crr_sizeof(20 / 21) */
+ *    version: the checksum verification of loaded states (cadence_load_verify.h), crr_sizeof(20 / 21); the branch
+ *    and routing decisions for tasks against loaded states (cadence_load_ndc.h), crr_sizeof(22..26) and
+ *    CRR_ERR_NDC_STATE_NOT_LOADED */
 #define CRR_ABI_VERSION 8
 
 /* ---- constants restated from the reference ------------------------------------------------ */
@@ -175,6 +177,7 @@ enum crr_status_code {
     CRR_ERR_NDC_FIRST_ITEM_MISMATCH = 22, /* BadRequest       versionHistory.go:474-476 AddVersionHistory      */
     CRR_ERR_NDC_RETRY_TASK = 23,          /* RetryTaskV2Error ndc/branch_manager.go:214-225 out-of-order batch */
     CRR_ERR_NDC_BAD_INDEX = 24,           /* BadRequest       versionHistory.go:442-444 invalid branch index   */
+    CRR_ERR_NDC_STATE_NOT_LOADED = 25,    /* cadence_load_ndc.h: the task's persisted state did not load   */
     CRR_ERR_CAPACITY = 100                /* engine: a slot table was sized too small by the host  */
 };
 
@@ -626,7 +629,9 @@ size_t crr_sizeof(int which);   /* 0 workflow, 1 exec row, 2 activity, 3 timer, 
                                    6 vh item, 7 reset point, 8 activity side, 9 start side,
                                    10 ndc task, 11 ndc result, 12 task row, 13 crr_inputs, 14 crr_outputs,
                                    cadence_load.h: 15 state blob, 16 state wf, 17 state batch, 18 load summary,
-                                   19 load image, cadence_load_verify.h: 20 stored checksum, 21 verify row */
+                                   19 load image, cadence_load_verify.h: 20 stored checksum, 21 verify row,
+                                   cadence_load_ndc.h: 22 replication task, 23 branch token, 24 load branches,
+                                   25 ndc plan, 26 ndc route */
 
 /* Host-side CRC32-IEEE (hash/crc32.ChecksumIEEE) used by the shim's standalone verify. */
 uint32_t crr_crc32_ieee(const uint8_t* data, size_t len);
