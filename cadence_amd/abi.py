@@ -343,6 +343,23 @@ class CLoadNdcSizes(ctypes.Structure):
                 ("n_out_items", ctypes.c_uint64), ("work_needed", ctypes.c_uint64)]
 
 
+# ---- the checksum to store for routed tasks (include/cadence_load_store.h) --------------------------------
+STORE_ROW = np.dtype([("value", "<u4"), ("outcome", "<i4"), ("payload_len", "<u4"), ("status", "<i4")])
+LAST_EVENT = np.dtype([("event_id", "<i8"), ("version", "<i8")])
+POSITION_NONE = 0xFFFFFFFF                    # the position map: the workflow is not in the resumed batch
+
+
+class StoreOutcome(enum.IntEnum):
+    APPLIED = 0
+    BACKFILLED = 1
+    NOT_LOADED = 2
+    NO_ROUTE = 3
+    NEW_BRANCH = 4
+    VH_ERROR = 5
+    NOT_RESUMED = 6
+    REPLAY_FAILED = 7
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -411,7 +428,8 @@ def check_layout(lib):
         if got != dt.itemsize:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {got} vs numpy {dt.itemsize}")
     for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize),
-                 (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize)):
+                 (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize),
+                 (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
     for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage),

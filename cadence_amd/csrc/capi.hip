@@ -7,6 +7,7 @@
 
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
+#include "cadence_load_store.h"
 #include "cadence_load_verify.h"
 #include "cadence_replay.h"
 #include "stream_device.h"
@@ -266,6 +267,8 @@ size_t crr_sizeof(int which) {
     case 24: return sizeof(crr_load_branches);
     case 25: return sizeof(crr_load_ndc_sizes);
     case 26: return sizeof(crr_ndc_route);
+    case 27: return sizeof(crr_store_row);
+    case 28: return sizeof(crr_last_event);
     default: return 0;
   }
 }

@@ -16,6 +16,9 @@
 //   branches_count_wf / branches_emit_wf   per workflow  (on request, cadence_load_ndc.h) every history of the
 //                              VersionHistories blob -> the branch table crr_ndc_prepare takes; task_row /
 //                              route_task per replication task around that call
+//   store_task   per task      (on request, cadence_load_store.h) the checksum to store once the routed task is
+//                              committed: the payload written once behind a state view (payload_head ...), from the
+//                              rows a resumed replay left or from the loaded image with the task's last event
 //
 // Wire format: thrift binary (big-endian; field header = type byte + i16 id, 0 ends a struct), field IDs of
 // .gen/go/sqlblobs/sqlblobs.go restated below (tests/golden/sqlblobs_fields.json pins them); a field whose
@@ -30,6 +33,7 @@
 
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
+#include "cadence_load_store.h"
 #include "cadence_load_verify.h"
 
 #if defined(__HIPCC__)
@@ -1231,6 +1235,246 @@ CRR_HD void route_task(const NdcWork& k, const crr_repl_task& t, uint32_t idx, u
     }
   }
   routes[idx] = o;
+}
+
+// ---- per task: the checksum to store once the routed task is committed (cadence_load_store.h) ---------------
+// The payload writer of generateMutableStateChecksum, written once behind a state view: the exec row, the ID of
+// live row j of pending map t, version-history item j of the current branch.  Every source of a state is this
+// one view -- the loader's scratch, a dense image, the slot tables a resumed replay wrote -- as a row pointer
+// and a stride per table (each table by name: with the constant table indices of the writer everything stays
+// in registers).  The counts are the caller's, already bounded by what the tables hold.
+struct StateView {
+  crr_exec_row R;
+  const uint8_t *act, *timer, *child, *rc, *sig;   // live row 0 of each pending map
+  const crr_vh_item* vh;                           // item 0 of the current branch
+  uint32_t n_act, n_timer, n_child, n_rc, n_sig, n_vh;
+  uint64_t stride;                                 // rows between two live rows
+
+  CRR_HD uint32_t count(int t) const { return t == 0 ? n_act : t == 1 ? n_timer : t == 2 ? n_child : t == 3 ? n_rc : n_sig; }
+  CRR_HD int64_t id(int t, uint32_t j) const {     // the ID a row's first field
+    const uint8_t* p = t == 0 ? act : t == 1 ? timer : t == 2 ? child : t == 3 ? rc : sig;
+    int64_t v;
+    memcpy(&v, p + (uint64_t)j * stride * kRowBytes[t], sizeof v);
+    return v;
+  }
+  CRR_HD crr_vh_item item(uint32_t j) const { return vh[(uint64_t)j * stride]; }
+};
+
+// a count read from an exec row, bounded by the rows its table holds (none without a table)
+CRR_HD uint32_t bounded_count(int32_t n, int64_t room, const void* table) {
+  if (!table || n <= 0 || room <= 0) return 0;
+  return (uint32_t)((int64_t)n < room ? (int64_t)n : room);
+}
+
+// the state of workflow w as loaded: the fields verify_wf reads
+CRR_HD StateView scratch_view(const Ctx& c, uint32_t w) {
+  StateView S;
+  S.R = c.exec()[w];
+  auto row0 = [&](int t) { return c.rows(t) + (uint64_t)c.cnt(t)[w] * kRowBytes[t]; };
+  auto n = [&](int t) { return (uint32_t)(c.cnt(t)[w + 1] - c.cnt(t)[w]); };
+  S.act = row0(0), S.timer = row0(1), S.child = row0(2), S.rc = row0(3), S.sig = row0(4);
+  S.vh = reinterpret_cast<const crr_vh_item*>(row0(5));
+  S.n_act = n(0), S.n_timer = n(1), S.n_child = n(2), S.n_rc = n(3), S.n_sig = n(4), S.n_vh = n(5);
+  S.stride = 1;
+  return S;
+}
+
+// 0x59 + MutableStateChecksumPayload.Encode up to the histories' list header (fields and order as verify_wf
+// writes them); the caller writes the n_hist branches, then payload_tail
+CRR_HD void payload_head(Crc& K, const StateView& S, const uint8_t* sticky, uint32_t sticky_len, int32_t current,
+                         uint32_t n_hist) {
+  const crr_exec_row& R = S.R;
+  K.u8(0x59);                                                                   // preambleVersion0
+  K.field(T_BOOL, 10); K.u8((R.flags & CRR_EXEC_CANCEL_REQUESTED) ? 1 : 0);     // CancelRequested
+  K.field(T_I16, 15); K.be16((uint32_t)(uint16_t)(int16_t)R.state);             // State
+  K.field(T_I64, 23); K.be64(R.last_first_event_id);
+  K.field(T_I64, 24); K.be64(R.next_event_id);
+  K.field(T_I64, 25); K.be64(R.last_processed_event);
+  K.field(T_I64, 26); K.be64((int64_t)R.signal_count);
+  K.field(T_I32, 35); K.be32((uint32_t)(int32_t)R.decision_attempt);
+  K.field(T_I64, 36); K.be64(R.decision_version);
+  K.field(T_I64, 37); K.be64(R.decision_schedule_id);
+  K.field(T_I64, 38); K.be64(R.decision_started_id);
+  auto ids = [&](uint32_t field_id, int t) {
+    const uint32_t n = S.count(t);
+    K.list_header(field_id, T_I64, n);
+    for (uint32_t j = 0; j < n; ++j) K.be64(S.id(t, j));
+  };
+  ids(45, 1);   // PendingTimerStartedIDs
+  ids(46, 0);   // PendingActivityScheduledIDs
+  ids(47, 4);   // PendingSignalInitiatedIDs
+  ids(48, 3);   // PendingReqCancelInitiatedIDs
+  ids(49, 2);   // PendingChildInitiatedIDs
+  K.field(T_STRING, 55); K.binary(sticky, sticky_len);                          // StickyTaskListName
+  K.field(T_STRUCT, 56);                                                        // VersionHistories
+  K.field(T_I32, 10); K.be32((uint32_t)current);                                //   CurrentVersionHistoryIndex
+  K.list_header(20, T_STRUCT, n_hist);                                          //   Histories
+}
+CRR_HD void payload_branch(Crc& K, const uint8_t* token, uint32_t token_len, uint32_t n_items) {
+  K.field(T_STRING, 10); K.binary(token, token_len);                            //   VersionHistory.BranchToken
+  K.list_header(20, T_STRUCT, n_items);                                         //   VersionHistory.Items
+}
+CRR_HD void payload_item(Crc& K, int64_t event_id, int64_t version) {
+  K.field(T_I64, 10); K.be64(event_id);
+  K.field(T_I64, 20); K.be64(version);
+  K.u8(0);
+}
+CRR_HD void payload_branch_end(Crc& K) { K.u8(0); }
+CRR_HD void payload_tail(Crc& K) {
+  K.u8(0);   // VersionHistories stop
+  K.u8(0);   // payload stop
+}
+
+// what a call reads beside the loader's context: the tasks with their decisions and the resident branch table
+struct StoreIn {
+  const crr_repl_task* tasks;
+  const crr_last_event* last;
+  const crr_ndc_result* results;
+  const crr_ndc_route* routes;
+  crr_load_branches br;
+  uint64_t n_branches, n_items;   // the table's sizes: every index read from it is checked against them
+  uint32_t n_tasks;
+};
+
+// the post-replay state of a workflow in the slot tables of the resumed batch (crr_outputs), addressed as
+// load_place_kernel addresses them; have == false: no replay was run
+struct ReplayAfter {
+  const crr_workflow* wf;
+  const uint32_t* position;
+  crr_outputs out;
+  uint32_t n_pos, stride, wave_begin;
+  bool have;
+  CRR_HD bool view(uint32_t w, StateView& S) const {
+    if (!have) return false;
+    const uint32_t p = position ? position[w] : w;
+    if (p >= n_pos) return false;
+    const crr_workflow& D = wf[p];
+    if (!(D.flags & CRR_WF_FLAG_RESUME)) return false;
+    S.R = out.exec[p];
+    S.stride = p >= wave_begin ? 1 : stride;
+    auto row0 = [&](const void* table, int64_t base, int t) {
+      return static_cast<const uint8_t*>(table) + (uint64_t)base * kRowBytes[t];
+    };
+    S.act = row0(out.act, D.act_base, 0), S.timer = row0(out.timer, D.timer_base, 1), S.child = row0(out.child, D.child_base, 2);
+    S.rc = row0(out.rc, D.rc_base, 3), S.sig = row0(out.sig, D.sig_base, 4);
+    S.vh = reinterpret_cast<const crr_vh_item*>(row0(out.vh, D.vh_base, 5));
+    // a garbage row cannot send the lane out of its tables: every count is bounded by the descriptor's capacity
+    S.n_act = bounded_count(S.R.n_activity, D.act_cap, out.act), S.n_timer = bounded_count(S.R.n_timer, D.timer_cap, out.timer);
+    S.n_child = bounded_count(S.R.n_child, D.child_cap, out.child), S.n_rc = bounded_count(S.R.n_rc, D.rc_cap, out.rc);
+    S.n_sig = bounded_count(S.R.n_signal, D.sig_cap, out.sig), S.n_vh = bounded_count(S.R.n_vh_items, D.vh_cap, out.vh);
+    return true;
+  }
+};
+
+// the same from a dense image indexed by workflow (the host restatement); I == NULL: no replay was run
+struct ImageAfter {
+  const crr_load_image* I;
+  uint32_t n_wf;
+  CRR_HD bool view(uint32_t w, StateView& S) const {
+    if (!I || !I->exec || !I->offsets || (I->status && I->status[w] != 0)) return false;
+    S.R = I->exec[w];
+    S.stride = 1;
+    auto off = [&](int t) { return I->offsets[(uint64_t)t * ((uint64_t)n_wf + 1) + w]; };
+    auto row0 = [&](int t) { return I->rows[t] ? static_cast<const uint8_t*>(I->rows[t]) + (uint64_t)off(t) * kRowBytes[t] : nullptr; };
+    auto n = [&](int t, int32_t field) {
+      const int64_t o = off(t), e = I->offsets[(uint64_t)t * ((uint64_t)n_wf + 1) + w + 1];
+      return o < 0 ? 0u : bounded_count(field, e - o, I->rows[t]);
+    };
+    S.act = row0(0), S.timer = row0(1), S.child = row0(2), S.rc = row0(3), S.sig = row0(4);
+    S.vh = reinterpret_cast<const crr_vh_item*>(row0(5));
+    S.n_act = n(0, S.R.n_activity), S.n_timer = n(1, S.R.n_timer), S.n_child = n(2, S.R.n_child), S.n_rc = n(3, S.R.n_rc);
+    S.n_sig = n(4, S.R.n_signal), S.n_vh = n(5, S.R.n_vh_items);
+    return true;
+  }
+};
+
+// generateChecksum for task `idx` as CloseTransactionAsMutation reaches it on the task's route
+// (mutable_state_builder.go:3959-3996): the outcome's precedence is cadence_load_store.h's.  Nothing of the
+// payload is stored; a table that is not this batch's (ranges outside the sizes given) reads as not loaded.
+template <class After>
+CRR_HD void store_task(const Ctx& c, const StoreIn& a, const After& after, const uint32_t* tables, uint32_t idx,
+                       crr_store_row* result) {
+  crr_store_row o = {0, CRR_STORE_NOT_LOADED, 0, 0};
+  auto done = [&](int32_t outcome, int32_t status) {
+    o.outcome = outcome;
+    o.status = status;
+    result[idx] = o;
+  };
+  const crr_repl_task t = a.tasks[idx];
+  if (t.wf >= c.in.n_wf || c.status()[t.wf] != CRR_LOAD_OK) return done(CRR_STORE_NOT_LOADED, 0);
+  const uint32_t w = t.wf;
+  const ExecAux A = c.aux()[w];
+  const uint64_t total = c.in.blob_off[c.in.n_blobs];
+  const int64_t b0 = a.br.branch_begin[w], nb = a.br.branch_begin[w + 1] - b0;
+  const int32_t current = a.br.current[w];
+  if (b0 < 0 || nb <= 0 || (uint64_t)b0 + (uint64_t)nb > a.n_branches || nb != (int64_t)A.n_hist || current < 0 ||
+      current >= nb || A.sticky_off > total || A.sticky_len > total - A.sticky_off)
+    return done(CRR_STORE_NOT_LOADED, 0);
+  const crr_ndc_route rt = a.routes[idx];
+  const crr_ndc_result r = a.results[idx];
+  const bool apply = rt.route == CRR_ROUTE_APPLY_CURRENT;
+  if ((!apply && rt.route != CRR_ROUTE_NON_CURRENT) || r.action == CRR_NDC_DUPLICATE) return done(CRR_STORE_NO_ROUTE, 0);
+  StateView S;
+  if (apply) {
+    if (!after.view(w, S)) return done(CRR_STORE_NOT_RESUMED, 0);
+    if (S.R.status != CRR_OK) return done(CRR_STORE_REPLAY_FAILED, S.R.status);
+  }
+  if (r.action != CRR_NDC_APPEND) return done(CRR_STORE_NEW_BRANCH, 0);
+  const crr_last_event e = a.last[idx];
+  // NewVersionHistoryItem (versionHistory.go:37-43) comes before GetVersionHistory on the backfill's path
+  if (!apply && (e.event_id < 0 || (e.version < 0 && e.version != CRR_EMPTY_VERSION)))
+    return done(CRR_STORE_VH_ERROR, CRR_ERR_VH_INVALID_ITEM);
+  if (r.branch_index < 0 || r.branch_index >= nb || (apply && r.branch_index != current))
+    return done(CRR_STORE_VH_ERROR, CRR_ERR_NDC_BAD_INDEX);
+  const int64_t target = r.branch_index;
+  // a branch of the table, its ranges checked against the table's sizes and the batch's bytes
+  auto branch = [&](int64_t h, crr_ndc_branch& br, crr_branch_token& tk) {
+    br = a.br.branches[b0 + h];
+    tk = a.br.tokens[b0 + h];
+    return (uint64_t)br.item_begin + br.item_count <= a.n_items && tk.off <= total && tk.len <= total - tk.off;
+  };
+  int mode = 0;   // the target branch: 0 as it is, 1 the last item's event ID updated, 2 one item appended
+  if (!apply) {   // AddOrUpdateItem (versionHistory.go:193-226)
+    crr_ndc_branch br;
+    crr_branch_token tk;
+    if (!branch(target, br, tk)) return done(CRR_STORE_NOT_LOADED, 0);
+    mode = 2;
+    if (br.item_count) {
+      const crr_vh_item last = a.br.items[br.item_begin + br.item_count - 1];
+      if (e.version < last.version) return done(CRR_STORE_VH_ERROR, CRR_ERR_VH_LOWER_VERSION);
+      if (e.event_id <= last.event_id) return done(CRR_STORE_VH_ERROR, CRR_ERR_VH_EVENT_ID_NOT_INCREASING);
+      mode = e.version > last.version ? 2 : 1;
+    }
+    S = scratch_view(c, w);
+  }
+  Crc K;
+  K.init(tables);
+  // ApplyEvents clears stickiness before its loop (state_builder.go:108); the backfill keeps the name as stored
+  payload_head(K, S, c.in.bytes + (apply ? 0 : A.sticky_off), apply ? 0 : A.sticky_len, current, (uint32_t)nb);
+  for (int64_t h = 0; h < nb; ++h) {
+    crr_ndc_branch br;
+    crr_branch_token tk;
+    if (!branch(h, br, tk)) return done(CRR_STORE_NOT_LOADED, 0);
+    if (apply && h == target) {   // the current branch as the replay left it
+      payload_branch(K, c.in.bytes + tk.off, tk.len, S.n_vh);
+      for (uint32_t j = 0; j < S.n_vh; ++j) {
+        const crr_vh_item x = S.item(j);
+        payload_item(K, x.event_id, x.version);
+      }
+    } else {
+      const bool mine = !apply && h == target;
+      payload_branch(K, c.in.bytes + tk.off, tk.len, br.item_count + (mine && mode == 2 ? 1u : 0u));
+      const crr_vh_item* it = a.br.items + br.item_begin;
+      for (uint32_t j = 0; j < br.item_count; ++j)
+        payload_item(K, mine && mode == 1 && j + 1 == br.item_count ? e.event_id : it[j].event_id, it[j].version);
+      if (mine && mode == 2) payload_item(K, e.event_id, e.version);
+    }
+    payload_branch_end(K);
+  }
+  payload_tail(K);
+  o.payload_len = K.len;
+  o.value = K.finish();
+  done(apply ? CRR_STORE_APPLIED : CRR_STORE_BACKFILLED, 0);
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

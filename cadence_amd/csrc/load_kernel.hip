@@ -16,6 +16,8 @@
 //                       (cadence_load_ndc.h); load_ndc_scan_kernel between them, load_scan_kernel's pattern
 //   load_task_room_kernel / load_task_rows_kernel / load_route_kernel   one lane per replication task: its room for
 //                       new-branch items, its crr_ndc_task row, and after crr_ndc_prepare the routing decision
+//   load_store_kernel   one lane per replication task: the checksum to store once the task is committed, its payload
+//                       generated from the rows the resumed replay left or from the loaded image (cadence_load_store.h)
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -243,6 +245,17 @@ __global__ void __launch_bounds__(kBlock) load_route_kernel(NdcWork k, const crr
                                                             crr_ndc_route* routes) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < k.n_tasks) route_task(k, tasks[i], i, n_incoming, branches, items, out_items, results, routes);
+}
+
+// ---- cadence_load_store.h: the checksum to store for every routed task -----------------------------------------
+// one lane per task, load_verify_kernel's shape: the payload streamed through the CRC, nothing of it stored, the
+// tables built by the block in LDS (8 KB).  It walks no blob -- the branches come from the resident table -- so
+// it needs no skip stack.
+__global__ void __launch_bounds__(kBlock) load_store_kernel(Ctx c, StoreIn a, ReplayAfter after, crr_store_row* result) {
+  __shared__ uint32_t crc_tables[8 * 256];
+  build_crc_tables(crc_tables);
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < a.n_tasks) store_task(c, a, after, crc_tables, i, result);
 }
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
@@ -504,6 +517,64 @@ int crr_load_ndc_run(const crr_state_batch* in, const void* scratch, size_t scra
   if (rc != 0) return rc;
   hipLaunchKernelGGL(load_route_kernel, grid_of(P.n_tasks), dim3(kBlock), 0, s, k, tasks, P.n_incoming, dst->branches,
                      dst->items, out_items, results, routes);
+  return (int)hipGetLastError();
+}
+
+int crr_load_store_checksums(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                             const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                             const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                             const crr_ndc_route* routes, const crr_load_branches* branches,
+                             const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
+                             const crr_outputs* replay_out, const uint32_t* position, crr_store_row* result,
+                             void* stream) {
+  if (!in || !summary_host || !ndc_plan_host || ndc_plan_host->err != 0) return -1;
+  const crr_load_ndc_sizes& P = *ndc_plan_host;
+  if (in->n_blobs != summary_host->n_blobs || in->n_wf != summary_host->n_wf || P.n_wf != in->n_wf) return -1;   // not the planned batch
+  if (n_tasks > P.n_tasks) return -1;
+  Ctx c;
+  if (in->n_wf) {
+    if (!plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
+    if (in->n_blobs && (!in->bytes || !in->blob_off)) return -1;
+  } else {
+    memset(&c, 0, sizeof c);   // a batch without workflows has no plan to read: every task is not loaded
+  }
+  c.in = *in;
+  if ((replay_in == nullptr) != (replay_out == nullptr)) return -1;
+  if (replay_in) {
+    if (replay_in->n_wf && (!replay_in->wf || !replay_out->exec)) return -1;
+    if (replay_in->stride == 0 || ((replay_in->flags & CRR_IN_WAVE_TAIL) && replay_in->wave_begin > replay_in->n_wf)) return -1;
+  }
+  if (n_tasks) {
+    if (!tasks || !last_events || !results || !routes || !result || !branches) return -1;
+    if (in->n_wf && (!branches->branch_begin || !branches->current)) return -1;
+    if (P.n_branches && (!branches->branches || !branches->tokens)) return -1;
+    if (P.n_items && !branches->items) return -1;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_tasks == 0) return 0;
+  StoreIn a;
+  a.tasks = tasks;
+  a.last = last_events;
+  a.results = results;
+  a.routes = routes;
+  a.br = *branches;
+  a.n_branches = P.n_branches;
+  a.n_items = P.n_items;
+  a.n_tasks = n_tasks;
+  ReplayAfter after;
+  memset(&after, 0, sizeof after);
+  after.have = replay_in != nullptr;
+  if (replay_in) {
+    after.wf = replay_in->wf;
+    after.position = position;
+    after.out = *replay_out;
+    after.n_pos = replay_in->n_wf;
+    after.stride = replay_in->stride;
+    after.wave_begin = (replay_in->flags & CRR_IN_WAVE_TAIL) ? replay_in->wave_begin : replay_in->n_wf;
+  }
+  hipLaunchKernelGGL(load_store_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, a, after, result);
   return (int)hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // load_kernel.hip compile; this file runs its phases as loops (optionally over threads), with serial
 // prefix scans between them, over a scratch laid out exactly like the device's.
 // crr_load_states_verify_host (include/cadence_load_verify.h) runs the same load, then load_decode.h's verify_wf;
-// crr_load_branches_host (include/cadence_load_ndc.h) the same load, then its branch walk.
+// crr_load_branches_host (include/cadence_load_ndc.h) the same load, then its branch walk;
+// crr_load_store_checksums_host (include/cadence_load_store.h) both, then load_decode.h's store_task per task.
 #include <stdlib.h>
 
 #include <thread>
@@ -89,6 +90,29 @@ int run_load(const crr_state_batch* in, int threads, Ctx& c) {
 
 constexpr CrcTab kCrcTab = make_crc_tab();
 
+// the branch walk's count phase and its serial scans over a work buffer this allocates (the caller frees k.s):
+// 0, -2 out of memory
+int count_branches(const Ctx& c, int threads, NdcWork& k) {
+  const uint32_t n_wf = c.in.n_wf;
+  k.L = carve_ndc(n_wf, 0);
+  k.n_wf = n_wf;
+  k.n_tasks = 0;
+  k.s = static_cast<uint8_t*>(calloc(k.L.end + 16, 1));
+  if (!k.s) return -2;
+  parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_count_wf(c, k, w, stk); });
+  for (int t = 0; t < 2; ++t) {
+    int64_t* p = k.cnt(t);
+    int64_t run = 0;
+    for (uint32_t w = 0; w < n_wf; ++w) {
+      const int64_t x = p[w];
+      p[w] = run;
+      run += x;
+    }
+    p[n_wf] = run;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_image* dst, crr_load_summary* summary,
@@ -128,24 +152,9 @@ extern "C" int crr_load_branches_host(const crr_state_batch* in, const crr_load_
   if (rc != 0) return rc;
   const uint32_t n_wf = in->n_wf;
   NdcWork k;
-  k.L = carve_ndc(n_wf, 0);
-  k.n_wf = n_wf;
-  k.n_tasks = 0;
-  k.s = static_cast<uint8_t*>(calloc(k.L.end + 16, 1));
-  if (!k.s) {
+  if (count_branches(c, threads, k) != 0) {
     free(c.s);
     return -2;
-  }
-  parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_count_wf(c, k, w, stk); });
-  for (int t = 0; t < 2; ++t) {
-    int64_t* p = k.cnt(t);
-    int64_t run = 0;
-    for (uint32_t w = 0; w < n_wf; ++w) {
-      const int64_t x = p[w];
-      p[w] = run;
-      run += x;
-    }
-    p[n_wf] = run;
   }
   memset(plan, 0, sizeof *plan);
   plan->n_wf = n_wf;
@@ -159,6 +168,49 @@ extern "C" int crr_load_branches_host(const crr_state_batch* in, const crr_load_
   free(k.s);
   free(c.s);
   return 0;
+}
+
+// the checksum to store for routed tasks (include/cadence_load_store.h): the load and the branch walk as above into
+// a table of this call, then load_decode.h's store_task per task over the dense after-image
+extern "C" int crr_load_store_checksums_host(const crr_state_batch* in, const crr_repl_task* tasks,
+                                             const crr_last_event* last_events, uint32_t n_tasks,
+                                             const crr_ndc_result* results, const crr_ndc_route* routes,
+                                             const crr_load_image* after, crr_store_row* result, int threads) {
+  if (!in || (n_tasks && (!tasks || !last_events || !results || !routes || !result))) return -1;
+  if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
+  NdcWork k;
+  if (count_branches(c, threads, k) != 0) {
+    free(c.s);
+    return -2;
+  }
+  StoreIn a;
+  a.tasks = tasks;
+  a.last = last_events;
+  a.results = results;
+  a.routes = routes;
+  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
+  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
+  a.n_tasks = n_tasks;
+  // one block for the table (calloc(0) may be NULL: at least one element each)
+  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
+  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
+  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
+  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
+  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
+  const bool ok = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current;
+  if (ok) {
+    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
+    const ImageAfter img = {after, n_wf};
+    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { store_task(c, a, img, kCrcTab.v, i, result); });
+  }
+  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
+  free(k.s);
+  free(c.s);
+  return ok ? 0 : -2;
 }
 
 extern "C" int crr_load_states_verify_host(const crr_state_batch* in, const crr_stored_checksum* stored,

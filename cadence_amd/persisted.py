@@ -21,6 +21,10 @@ after materialising a state -- the stored ``checksum.Checksum`` against a freshl
 ``StateLoader.ndc_prepare`` decides and routes replication tasks against those states on the device
 (``include/cadence_load_ndc.h``): ``prepareVersionHistory`` through ``crr_ndc_prepare``, then
 ``prepareMutableState``'s route per task; ``apply_mask`` turns the routes into the workflows to resume.
+
+``StateLoader.store_checksums`` / ``store_checksums_host`` give, per routed task, the checksum Go stores with the
+state when it commits the task (``include/cadence_load_store.h``): from the rows the resumed replay left for a
+task applied to the current branch, from the loaded image for one backfilled onto another branch.
 """
 from __future__ import annotations
 
@@ -461,6 +465,8 @@ def _host_lib():
         L.crr_load_states_verify_host.restype = ctypes.c_int
         L.crr_load_branches_host.argtypes = [vp, vp, vp, ctypes.c_int]
         L.crr_load_branches_host.restype = ctypes.c_int
+        L.crr_load_store_checksums_host.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int]
+        L.crr_load_store_checksums_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -563,6 +569,61 @@ def load_branches_host(sbs: StateBlobSet, threads: int = 1) -> Branches:
     return out
 
 
+# ---- the checksum to store once a routed task is committed (include/cadence_load_store.h) ----------------------
+def _after_image(after: Optional[LoadedStates], n_wf: int):
+    """``crr_load_image`` over the post-replay states (``ReplayResult.to_loaded``, canonical workflow order; a
+    workflow outside its mask counts as not resumed): (the struct or None, the arrays it points into)."""
+    if after is None:
+        return None, ()
+    if after.exec.shape[0] != n_wf:
+        raise ValueError(f"after: {after.exec.shape[0]} states for {n_wf} workflows")
+    keep = [np.ascontiguousarray(after.exec, dtype=abi.EXEC_ROW), np.zeros((abi.LOAD_TABLES, n_wf + 1), np.int64),
+            np.ascontiguousarray(~np.asarray(after.mask, bool), dtype=np.int32)]
+    c = abi.CLoadImage()
+    c.exec, c.offsets, c.status = (a.ctypes.data if a.size else None for a in keep)
+    for t, name in enumerate(abi.LOAD_ROW_TABLES):
+        keep[1][t, 1:] = np.cumsum(after.counts(name))
+        rows = np.ascontiguousarray(after.rows[name], dtype=_ROW_DTYPES[name])
+        if rows.shape[0] != int(keep[1][t, n_wf]):
+            raise ValueError(f"after: {rows.shape[0]} {name} rows for counts of {int(keep[1][t, n_wf])}")
+        keep.append(rows)
+        c.rows[t] = rows.ctypes.data if rows.size else None
+    return c, keep
+
+
+def _task_arrays(tasks, last_events, results=None, routes=None):
+    tasks = np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
+    n = int(tasks.shape[0])
+    out = [tasks, np.ascontiguousarray(last_events, dtype=abi.LAST_EVENT)]
+    if results is not None:
+        out += [np.ascontiguousarray(results, dtype=abi.NDC_RESULT), np.ascontiguousarray(routes, dtype=abi.NDC_ROUTE)]
+    for a in out:
+        if a.shape != (n,):
+            raise ValueError(f"{a.shape} rows for {n} tasks")
+    return out
+
+
+def store_checksums_host(sbs: StateBlobSet, tasks, last_events, results, routes, after: Optional[LoadedStates] = None,
+                         threads: int = 1) -> np.ndarray:
+    """The checksum to store with each task's state once the task is committed, by the host restatement
+    (``crr_load_store_checksums_host``): ``abi.STORE_ROW`` per task.  ``results`` / ``routes``: the decisions of
+    ``ndc_prepare``; ``last_events``: ``abi.LAST_EVENT`` per task; ``after``: the states the resumed replay left
+    (``ReplayResult.to_loaded``), None: no task can be ``APPLIED``."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
+    img, _keep = _after_image(after, sbs.n_wf)
+    out = np.zeros(tasks.shape[0], abi.STORE_ROW)
+
+    def ptr(a):
+        return a.ctypes.data if a.size else None
+    rc = L.crr_load_store_checksums_host(ctypes.byref(c), ptr(tasks), ptr(last), int(tasks.shape[0]), ptr(results), ptr(routes),
+                                         ctypes.byref(img) if img is not None else None, ptr(out), threads)
+    if rc != 0:
+        raise RuntimeError(f"crr_load_store_checksums_host failed: {rc}")
+    return out
+
+
 def apply_mask(routes: np.ndarray, tasks: Optional[np.ndarray] = None, n_wf: Optional[int] = None) -> np.ndarray:
     """The workflows whose task is to be replayed onto the placed rows (``ROUTE_APPLY_CURRENT``), as
     ``LoadedImage.resumable(mask=...)`` takes them (canonical workflow order; ``replication.BlobReplication``'s
@@ -632,6 +693,9 @@ class StateLoader:
         L.crr_load_ndc_plan.restype = ctypes.c_int
         L.crr_load_ndc_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp, vp]
         L.crr_load_ndc_run.restype = ctypes.c_int
+        L.crr_load_store_checksums.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32] + [vp] * 9
+        L.crr_load_store_checksums.restype = ctypes.c_int
+        self.last_ndc = None
         self.scratch = None
         self.scratch_bytes = 0
         self.summary = None
@@ -795,3 +859,46 @@ class StateLoader:
         self.last_out_begin = host("out_begin", np.uint32, n)
         return (host("results", abi.NDC_RESULT, n), host("routes", abi.NDC_ROUTE, n),
                 host("out_items", abi.VH_ITEM, int(br.plan.n_out_items)))
+
+    # ---- include/cadence_load_store.h ----------------------------------------------------------------------
+    def store_checksums(self, ds: DeviceStates, tasks, last_events, db=None, on_device: bool = False, perm=None):
+        """The checksum to store with each task's state once the task is committed (``crr_load_store_checksums``),
+        for the ``tasks`` the last ``ndc_prepare`` decided against the last plan's states (``self.last_ndc``: its
+        decisions, routes and branch table stay on the device): ``abi.STORE_ROW`` per task.  ``last_events``:
+        ``abi.LAST_EVENT`` per task.  ``db``: the resumed batch (an ``engine.DeviceBatch``) after its replay was
+        enqueued, for the tasks routed to the current branch; the position map is the inverse of ``perm`` (default:
+        the batch's own, as in ``place``).  Enqueued on the current stream; ``on_device``: the rows as a device byte
+        tensor, nothing copied back."""
+        from .engine import _dev_bytes
+        if self.last_ndc is None:
+            raise RuntimeError("store_checksums: no ndc_prepare to take the decisions from")
+        torch, dev = self.torch, self.engine.dev
+        br, out = self.last_ndc
+        tasks, last = _task_arrays(tasks, last_events)
+        n, n_wf = int(tasks.shape[0]), int(ds.c.n_wf)
+        if n > int(br.plan.n_tasks):
+            raise ValueError(f"{n} tasks, {int(br.plan.n_tasks)} decided")
+        T = {"tasks": _dev_bytes(torch, tasks, dev), "last": _dev_bytes(torch, last, dev),
+             "rows": torch.empty(max(n, 1) * abi.STORE_ROW.itemsize, dtype=torch.uint8, device=dev)}
+        if db is not None and perm is None:
+            perm = db.batch.perm
+        if db is not None and perm is not None:
+            perm = np.asarray(perm, np.int64)
+            pos = np.full(n_wf, abi.POSITION_NONE, np.uint32)
+            here = np.nonzero((perm >= 0) & (perm < n_wf))[0]
+            pos[perm[here]] = here
+            T["position"] = _dev_bytes(torch, pos, dev)
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+        rc = self.lib.crr_load_store_checksums(
+            ctypes.byref(ds.c), ptr(self.scratch), ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
+            ptr(T["tasks"]), ptr(T["last"]), n, ptr(out["results"]), ptr(out["routes"]), ctypes.byref(br.c), ctypes.byref(br.plan),
+            ctypes.byref(db.c_in) if db is not None else None, ctypes.byref(db.c_out) if db is not None else None,
+            ptr(T.get("position")), ptr(T["rows"]), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_store_checksums failed: {rc}")
+        self.last_store = T   # alive until the stream has run the kernel
+        if on_device:
+            return T["rows"]
+        return T["rows"][:n * abi.STORE_ROW.itemsize].cpu().numpy().view(abi.STORE_ROW).copy()
