@@ -360,6 +360,15 @@ class StoreOutcome(enum.IntEnum):
     REPLAY_FAILED = 7
 
 
+# ---- the VersionHistories blob to store for routed tasks (include/cadence_load_store_vh.h) ----------------
+VH_BLOB_ROW = np.dtype([("len", "<u4"), ("outcome", "<i4"), ("status", "<i4"), ("reserved", "<u4")])
+
+
+class CVhBlobSizes(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_int32), ("n_tasks", ctypes.c_uint32), ("n_generated", ctypes.c_uint64),
+                ("n_bytes", ctypes.c_uint64), ("work_needed", ctypes.c_uint64)]
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -429,10 +438,10 @@ def check_layout(lib):
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {got} vs numpy {dt.itemsize}")
     for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize),
                  (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize),
-                 (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize)):
+                 (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize), (30, VH_BLOB_ROW.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
     for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage),
-                  (24, CLoadBranches), (25, CLoadNdcSizes)):
+                  (24, CLoadBranches), (25, CLoadNdcSizes), (31, CVhBlobSizes)):
         if lib.crr_sizeof(i) != ctypes.sizeof(st):
             raise RuntimeError(f"ABI layout mismatch for {st.__name__}: C {lib.crr_sizeof(i)} vs ctypes {ctypes.sizeof(st)}")

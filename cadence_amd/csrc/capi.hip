@@ -8,6 +8,7 @@
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
 #include "cadence_load_store.h"
+#include "cadence_load_store_vh.h"
 #include "cadence_load_verify.h"
 #include "cadence_replay.h"
 #include "stream_device.h"
@@ -269,6 +270,8 @@ size_t crr_sizeof(int which) {
     case 26: return sizeof(crr_ndc_route);
     case 27: return sizeof(crr_store_row);
     case 28: return sizeof(crr_last_event);
+    case 30: return sizeof(crr_vh_blob_row);
+    case 31: return sizeof(crr_vh_blob_sizes);
     default: return 0;
   }
 }

@@ -34,6 +34,7 @@
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
 #include "cadence_load_store.h"
+#include "cadence_load_store_vh.h"
 #include "cadence_load_verify.h"
 
 #if defined(__HIPCC__)
@@ -1310,16 +1311,21 @@ CRR_HD void payload_head(Crc& K, const StateView& S, const uint8_t* sticky, uint
   K.field(T_I32, 10); K.be32((uint32_t)current);                                //   CurrentVersionHistoryIndex
   K.list_header(20, T_STRUCT, n_hist);                                          //   Histories
 }
-CRR_HD void payload_branch(Crc& K, const uint8_t* token, uint32_t token_len, uint32_t n_items) {
+// the three writers of a VersionHistory are templates on the sink: the CRC here, a byte sink for the blob to store
+// (cadence_load_store_vh.h)
+template <class Sink>
+CRR_HD void payload_branch(Sink& K, const uint8_t* token, uint32_t token_len, uint32_t n_items) {
   K.field(T_STRING, 10); K.binary(token, token_len);                            //   VersionHistory.BranchToken
   K.list_header(20, T_STRUCT, n_items);                                         //   VersionHistory.Items
 }
-CRR_HD void payload_item(Crc& K, int64_t event_id, int64_t version) {
+template <class Sink>
+CRR_HD void payload_item(Sink& K, int64_t event_id, int64_t version) {
   K.field(T_I64, 10); K.be64(event_id);
   K.field(T_I64, 20); K.be64(version);
   K.u8(0);
 }
-CRR_HD void payload_branch_end(Crc& K) { K.u8(0); }
+template <class Sink>
+CRR_HD void payload_branch_end(Sink& K) { K.u8(0); }
 CRR_HD void payload_tail(Crc& K) {
   K.u8(0);   // VersionHistories stop
   K.u8(0);   // payload stop
@@ -1388,17 +1394,38 @@ struct ImageAfter {
   }
 };
 
-// generateChecksum for task `idx` as CloseTransactionAsMutation reaches it on the task's route
-// (mutable_state_builder.go:3959-3996): the outcome's precedence is cadence_load_store.h's.  Nothing of the
-// payload is stored; a table that is not this batch's (ranges outside the sizes given) reads as not loaded.
+// What CloseTransactionAsMutation commits for task `idx` on its route (mutable_state_builder.go:3959-3996), decided
+// once for everything that is generated from it -- the checksum (store_task) and the VersionHistories blob
+// (cadence_load_store_vh.h): the outcome with cadence_load_store.h's precedence, its status, and for a generated
+// task the view its scalars and current branch come from and what AddOrUpdateItem does to the target branch.
+struct StoreDecision {
+  int32_t outcome, status;
+  bool apply;                 // the current route: the state as the resumed replay left it (S)
+  int mode;                   // the target branch: 0 as it is, 1 the last item's event ID updated, 2 one item appended
+  uint32_t w;
+  int32_t current;
+  int64_t b0, nb, target;     // the workflow's branches in the table, the task's among them
+  uint64_t total;             // the batch's bytes
+  uint64_t sticky_off;
+  uint32_t sticky_len;
+  crr_last_event e;
+  StateView S;
+  CRR_HD bool generated() const { return outcome == CRR_STORE_APPLIED || outcome == CRR_STORE_BACKFILLED; }
+};
+
+// a branch of the table, its ranges checked against the table's sizes and the batch's bytes
+CRR_HD bool table_branch(const StoreIn& a, int64_t b, uint64_t total, crr_ndc_branch& br, crr_branch_token& tk) {
+  br = a.br.branches[b];
+  tk = a.br.tokens[b];
+  return (uint64_t)br.item_begin + br.item_count <= a.n_items && tk.off <= total && tk.len <= total - tk.off;
+}
+
+// A table that is not this batch's (ranges outside the sizes given) reads as not loaded.
 template <class After>
-CRR_HD void store_task(const Ctx& c, const StoreIn& a, const After& after, const uint32_t* tables, uint32_t idx,
-                       crr_store_row* result) {
-  crr_store_row o = {0, CRR_STORE_NOT_LOADED, 0, 0};
+CRR_HD void store_decide(const Ctx& c, const StoreIn& a, const After& after, uint32_t idx, StoreDecision& D) {
   auto done = [&](int32_t outcome, int32_t status) {
-    o.outcome = outcome;
-    o.status = status;
-    result[idx] = o;
+    D.outcome = outcome;
+    D.status = status;
   };
   const crr_repl_task t = a.tasks[idx];
   if (t.wf >= c.in.n_wf || c.status()[t.wf] != CRR_LOAD_OK) return done(CRR_STORE_NOT_LOADED, 0);
@@ -1410,14 +1437,15 @@ CRR_HD void store_task(const Ctx& c, const StoreIn& a, const After& after, const
   if (b0 < 0 || nb <= 0 || (uint64_t)b0 + (uint64_t)nb > a.n_branches || nb != (int64_t)A.n_hist || current < 0 ||
       current >= nb || A.sticky_off > total || A.sticky_len > total - A.sticky_off)
     return done(CRR_STORE_NOT_LOADED, 0);
+  D.w = w, D.current = current, D.b0 = b0, D.nb = nb, D.total = total;
+  D.sticky_off = A.sticky_off, D.sticky_len = A.sticky_len;
   const crr_ndc_route rt = a.routes[idx];
   const crr_ndc_result r = a.results[idx];
   const bool apply = rt.route == CRR_ROUTE_APPLY_CURRENT;
   if ((!apply && rt.route != CRR_ROUTE_NON_CURRENT) || r.action == CRR_NDC_DUPLICATE) return done(CRR_STORE_NO_ROUTE, 0);
-  StateView S;
   if (apply) {
-    if (!after.view(w, S)) return done(CRR_STORE_NOT_RESUMED, 0);
-    if (S.R.status != CRR_OK) return done(CRR_STORE_REPLAY_FAILED, S.R.status);
+    if (!after.view(w, D.S)) return done(CRR_STORE_NOT_RESUMED, 0);
+    if (D.S.R.status != CRR_OK) return done(CRR_STORE_REPLAY_FAILED, D.S.R.status);
   }
   if (r.action != CRR_NDC_APPEND) return done(CRR_STORE_NEW_BRANCH, 0);
   const crr_last_event e = a.last[idx];
@@ -1426,55 +1454,246 @@ CRR_HD void store_task(const Ctx& c, const StoreIn& a, const After& after, const
     return done(CRR_STORE_VH_ERROR, CRR_ERR_VH_INVALID_ITEM);
   if (r.branch_index < 0 || r.branch_index >= nb || (apply && r.branch_index != current))
     return done(CRR_STORE_VH_ERROR, CRR_ERR_NDC_BAD_INDEX);
-  const int64_t target = r.branch_index;
-  // a branch of the table, its ranges checked against the table's sizes and the batch's bytes
-  auto branch = [&](int64_t h, crr_ndc_branch& br, crr_branch_token& tk) {
-    br = a.br.branches[b0 + h];
-    tk = a.br.tokens[b0 + h];
-    return (uint64_t)br.item_begin + br.item_count <= a.n_items && tk.off <= total && tk.len <= total - tk.off;
-  };
-  int mode = 0;   // the target branch: 0 as it is, 1 the last item's event ID updated, 2 one item appended
+  D.apply = apply, D.target = r.branch_index, D.e = e, D.mode = 0;
   if (!apply) {   // AddOrUpdateItem (versionHistory.go:193-226)
     crr_ndc_branch br;
     crr_branch_token tk;
-    if (!branch(target, br, tk)) return done(CRR_STORE_NOT_LOADED, 0);
-    mode = 2;
+    if (!table_branch(a, b0 + D.target, total, br, tk)) return done(CRR_STORE_NOT_LOADED, 0);
+    D.mode = 2;
     if (br.item_count) {
       const crr_vh_item last = a.br.items[br.item_begin + br.item_count - 1];
       if (e.version < last.version) return done(CRR_STORE_VH_ERROR, CRR_ERR_VH_LOWER_VERSION);
       if (e.event_id <= last.event_id) return done(CRR_STORE_VH_ERROR, CRR_ERR_VH_EVENT_ID_NOT_INCREASING);
-      mode = e.version > last.version ? 2 : 1;
+      D.mode = e.version > last.version ? 2 : 1;
     }
-    S = scratch_view(c, w);
+    D.S = scratch_view(c, w);
+  }
+  done(apply ? CRR_STORE_APPLIED : CRR_STORE_BACKFILLED, 0);
+}
+
+// branch h of a generated task as the commit writes it (the table of DESIGN.md §4, "The value to store"): the
+// token always from the persisted bytes; on the current route the current branch's items the replay's vh rows,
+// every other branch the table's, the backfill's target with AddOrUpdateItem(last event) applied
+struct StoreBranch {
+  crr_branch_token tk;
+  const crr_vh_item* it;      // item 0 of the source
+  uint64_t stride;            // rows between two items of the source
+  uint32_t n_src;             // items the source holds
+  uint32_t n;                 // items written: n_src, and one more when the last event is appended
+  bool update_last;           // the last source item's event ID becomes the last event's
+  CRR_HD crr_vh_item item(uint32_t j, const crr_last_event& e) const {
+    if (j >= n_src) return crr_vh_item{e.event_id, e.version};
+    crr_vh_item x = it[(uint64_t)j * stride];
+    if (update_last && j + 1 == n_src) x.event_id = e.event_id;
+    return x;
+  }
+};
+CRR_HD bool store_branch(const StoreIn& a, const StoreDecision& D, int64_t h, StoreBranch& B) {
+  crr_ndc_branch br;
+  if (!table_branch(a, D.b0 + h, D.total, br, B.tk)) return false;
+  if (D.apply && h == D.target) {   // the current branch as the replay left it
+    B.it = D.S.vh, B.stride = D.S.stride, B.n_src = B.n = D.S.n_vh, B.update_last = false;
+    return true;
+  }
+  const bool mine = !D.apply && h == D.target;
+  B.it = a.br.items + br.item_begin, B.stride = 1, B.n_src = br.item_count;
+  B.n = br.item_count + (mine && D.mode == 2 ? 1u : 0u);
+  B.update_last = mine && D.mode == 1;
+  return true;
+}
+
+// generateChecksum for task `idx` as CloseTransactionAsMutation reaches it on the task's route.  Nothing of the
+// payload is stored.
+template <class After>
+CRR_HD void store_task(const Ctx& c, const StoreIn& a, const After& after, const uint32_t* tables, uint32_t idx,
+                       crr_store_row* result) {
+  crr_store_row o = {0, CRR_STORE_NOT_LOADED, 0, 0};
+  StoreDecision D;
+  store_decide(c, a, after, idx, D);
+  o.outcome = D.outcome, o.status = D.status;
+  if (!D.generated()) {
+    result[idx] = o;
+    return;
   }
   Crc K;
   K.init(tables);
   // ApplyEvents clears stickiness before its loop (state_builder.go:108); the backfill keeps the name as stored
-  payload_head(K, S, c.in.bytes + (apply ? 0 : A.sticky_off), apply ? 0 : A.sticky_len, current, (uint32_t)nb);
-  for (int64_t h = 0; h < nb; ++h) {
-    crr_ndc_branch br;
-    crr_branch_token tk;
-    if (!branch(h, br, tk)) return done(CRR_STORE_NOT_LOADED, 0);
-    if (apply && h == target) {   // the current branch as the replay left it
-      payload_branch(K, c.in.bytes + tk.off, tk.len, S.n_vh);
-      for (uint32_t j = 0; j < S.n_vh; ++j) {
-        const crr_vh_item x = S.item(j);
-        payload_item(K, x.event_id, x.version);
-      }
-    } else {
-      const bool mine = !apply && h == target;
-      payload_branch(K, c.in.bytes + tk.off, tk.len, br.item_count + (mine && mode == 2 ? 1u : 0u));
-      const crr_vh_item* it = a.br.items + br.item_begin;
-      for (uint32_t j = 0; j < br.item_count; ++j)
-        payload_item(K, mine && mode == 1 && j + 1 == br.item_count ? e.event_id : it[j].event_id, it[j].version);
-      if (mine && mode == 2) payload_item(K, e.event_id, e.version);
+  payload_head(K, D.S, c.in.bytes + (D.apply ? 0 : D.sticky_off), D.apply ? 0 : D.sticky_len, D.current, (uint32_t)D.nb);
+  for (int64_t h = 0; h < D.nb; ++h) {
+    StoreBranch B;
+    if (!store_branch(a, D, h, B)) {
+      o.outcome = CRR_STORE_NOT_LOADED;
+      result[idx] = o;
+      return;
+    }
+    payload_branch(K, c.in.bytes + B.tk.off, B.tk.len, B.n);
+    for (uint32_t j = 0; j < B.n; ++j) {
+      const crr_vh_item x = B.item(j, D.e);
+      payload_item(K, x.event_id, x.version);
     }
     payload_branch_end(K);
   }
   payload_tail(K);
   o.payload_len = K.len;
   o.value = K.finish();
-  done(apply ? CRR_STORE_APPLIED : CRR_STORE_BACKFILLED, 0);
+  result[idx] = o;
+}
+
+// ---- per task: the VersionHistories blob to store (cadence_load_store_vh.h) --------------------------------
+// SerializeVersionHistories' thriftrw DataBlob (common/persistence/serializer.go:178-183): 0x59, then the struct
+// payload_head .. payload_branch_end stream into the CRC inside field 56.  Go writes every field of the three
+// structs, so every width is fixed: 16 bytes of head, per history 7 + token + 8 + 23 per item + 1, one stop byte.
+constexpr uint64_t kVhHead = 16, kVhHistory = 16, kVhItem = 23;
+
+// the blob's length for a generated task; false: a branch of the table is not this batch's (not loaded)
+CRR_HD bool vh_blob_len(const StoreIn& a, const StoreDecision& D, uint64_t& len) {
+  len = kVhHead + 1;
+  for (int64_t h = 0; h < D.nb; ++h) {
+    StoreBranch B;
+    if (!store_branch(a, D, h, B)) return false;
+    len += kVhHistory + B.tk.len + kVhItem * B.n;
+  }
+  return len <= 0xFFFFFFFFull;
+}
+
+// task idx's row and length: the decision of store_task, a branch that fails its check included
+template <class After>
+CRR_HD uint64_t vh_size_task(const Ctx& c, const StoreIn& a, const After& after, uint32_t idx, crr_vh_blob_row* rows) {
+  StoreDecision D;
+  store_decide(c, a, after, idx, D);
+  crr_vh_blob_row o = {0, D.outcome, D.status, 0};
+  uint64_t len = 0;
+  if (D.generated()) {
+    if (vh_blob_len(a, D, len)) o.len = (uint32_t)len;
+    else o.outcome = CRR_STORE_NOT_LOADED, len = 0;
+  }
+  rows[idx] = o;
+  return len;
+}
+
+// the plain sequential writer (the host restatement): bytes past `cap` are counted, not written
+struct ByteSink {
+  uint8_t* p;
+  uint64_t cap, len;
+  CRR_HD void u8(uint32_t b) {
+    if (len < cap) p[len] = (uint8_t)b;
+    ++len;
+  }
+  CRR_HD void be32(uint32_t v) {
+    for (int i = 3; i >= 0; --i) u8(v >> (8 * i));
+  }
+  CRR_HD void be64(int64_t v) {
+    for (int i = 7; i >= 0; --i) u8((uint32_t)((uint64_t)v >> (8 * i)));
+  }
+  CRR_HD void field(uint32_t type, uint32_t id) { u8(type), u8(id >> 8), u8(id); }
+  CRR_HD void list_header(uint32_t id, uint32_t elem, uint32_t n) { field(T_LIST, id), u8(elem), be32(n); }
+  CRR_HD void binary(const uint8_t* q, uint32_t n) {
+    be32(n);
+    for (uint32_t i = 0; i < n; ++i) u8(q[i]);
+  }
+};
+template <class Sink>
+CRR_HD bool vh_blob_write(Sink& K, const Ctx& c, const StoreIn& a, const StoreDecision& D) {
+  K.u8(0x59);                                                                   // preambleVersion0
+  K.field(T_I32, 10); K.be32((uint32_t)D.current);                              // CurrentVersionHistoryIndex
+  K.list_header(20, T_STRUCT, (uint32_t)D.nb);                                  // Histories
+  for (int64_t h = 0; h < D.nb; ++h) {
+    StoreBranch B;
+    if (!store_branch(a, D, h, B)) return false;
+    payload_branch(K, c.in.bytes + B.tk.off, B.tk.len, B.n);
+    for (uint32_t j = 0; j < B.n; ++j) {
+      const crr_vh_item x = B.item(j, D.e);
+      payload_item(K, x.event_id, x.version);
+    }
+    payload_branch_end(K);
+  }
+  K.u8(0);                                                                      // VersionHistories stop
+  return true;
+}
+
+// The output-stationary form (load_store_vh_emit_kernel): bytes [16 * chunk, + 16) of the concatenated blobs as
+// two little-endian words, whatever blobs they belong to.  The task that holds a byte is found by an upper-bound
+// search over the plan's prefix (runs of zero-length tasks are stepped over), the history by walking the task's
+// branches' lengths; inside a history the layout is closed-form.  A byte whose lookup fails -- a task the
+// decision no longer generates, an offset past what its branches give now -- is zero; the lane reads blob_off
+// within [0, n_tasks] only, and what it writes is the caller's 16 bytes.
+CRR_HD uint32_t be_byte(uint64_t v, uint32_t width, uint32_t i) { return (uint32_t)(v >> (8 * (width - 1 - i))) & 0xffu; }
+
+template <class After>
+CRR_HD void vh_emit_chunk(const Ctx& c, const StoreIn& a, const After& after, const uint64_t* blob_off, uint64_t n_bytes,
+                          uint64_t chunk, uint64_t& lo, uint64_t& hi) {
+  lo = hi = 0;
+  const uint64_t pos = chunk * 16;
+  if (pos >= n_bytes || a.n_tasks == 0) return;
+  uint32_t k = 0, r = a.n_tasks;   // the last task that starts at or before pos: blob_off[0] == 0
+  while (k + 1 < r) {
+    const uint32_t m = k + (r - k) / 2;
+    if (blob_off[m] <= pos) k = m;
+    else r = m;
+  }
+  uint64_t base = blob_off[k], end = blob_off[k + 1];
+  StoreDecision D;
+  StoreBranch B;
+  bool fresh = true, gen = false;
+  int64_t h = -1;
+  uint64_t h_begin = 0, h_end = kVhHead;
+  uint32_t j_have = 0xFFFFFFFFu;
+  crr_vh_item x = {0, 0};
+  for (uint32_t b = 0; b < 16; ++b) {
+    const uint64_t g = pos + b;
+    if (g >= n_bytes) return;
+    while (g >= end) {   // the next task that holds bytes
+      if (++k >= a.n_tasks) return;
+      base = blob_off[k], end = blob_off[k + 1];
+      fresh = true;
+    }
+    if (fresh) {
+      store_decide(c, a, after, k, D);
+      gen = D.generated() && g >= base;
+      h = -1, h_begin = 0, h_end = kVhHead;
+      fresh = false;
+    }
+    if (!gen) continue;
+    const uint64_t p = g - base;
+    uint32_t v = 0;
+    if (p < kVhHead) {
+      v = p == 0 ? 0x59u : p < 8 ? be_byte((0x08000aull << 32) | (uint32_t)D.current, 7, (uint32_t)p - 1)
+                                 : be_byte((0x0f00140cull << 32) | (uint32_t)D.nb, 8, (uint32_t)p - 8);
+    } else {
+      while (p >= h_end && h < D.nb) {
+        if (++h >= D.nb) break;
+        if (!store_branch(a, D, h, B)) {
+          gen = false;
+          break;
+        }
+        h_begin = h_end;
+        h_end = h_begin + kVhHistory + B.tk.len + kVhItem * B.n;
+        j_have = 0xFFFFFFFFu;
+      }
+      if (!gen) continue;
+      if (h < D.nb) {   // (past the last history: the struct's stop byte, zero like everything behind it)
+        const uint64_t q = p - h_begin, items_at = 15ull + B.tk.len;
+        if (q < 7) {
+          v = be_byte((0x0b000aull << 32) | B.tk.len, 7, (uint32_t)q);
+        } else if (q < 7ull + B.tk.len) {
+          v = c.in.bytes[B.tk.off + (q - 7)];
+        } else if (q < items_at) {
+          v = be_byte((0x0f00140cull << 32) | B.n, 8, (uint32_t)(q - 7 - B.tk.len));
+        } else if (q < items_at + kVhItem * B.n) {
+          const uint64_t rem = q - items_at;
+          const uint32_t j = (uint32_t)(rem / kVhItem), m = (uint32_t)(rem % kVhItem);
+          if (j != j_have) {
+            x = B.item(j, D.e);
+            j_have = j;
+          }
+          v = m < 3 ? be_byte(0x0a000aull, 3, m) : m < 11 ? be_byte((uint64_t)x.event_id, 8, m - 3)
+              : m < 14 ? be_byte(0x0a0014ull, 3, m - 11) : m < 22 ? be_byte((uint64_t)x.version, 8, m - 14) : 0u;
+        }
+      }
+    }
+    if (b < 8) lo |= (uint64_t)v << (8 * b);
+    else hi |= (uint64_t)v << (8 * (b - 8));
+  }
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

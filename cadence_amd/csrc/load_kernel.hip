@@ -18,6 +18,9 @@
 //                       new-branch items, its crr_ndc_task row, and after crr_ndc_prepare the routing decision
 //   load_store_kernel   one lane per replication task: the checksum to store once the task is committed, its payload
 //                       generated from the rows the resumed replay left or from the loaded image (cadence_load_store.h)
+//   load_store_vh_size_kernel / load_store_vh_emit_kernel   the VersionHistories blob to store for the same tasks
+//                       (cadence_load_store_vh.h): one lane per task sizes it, load_ndc_scan_kernel gives the offsets,
+//                       then one lane per 16 bytes of the output writes them with one dwordx4 store
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -256,6 +259,31 @@ __global__ void __launch_bounds__(kBlock) load_store_kernel(Ctx c, StoreIn a, Re
   build_crc_tables(crc_tables);
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i < a.n_tasks) store_task(c, a, after, crc_tables, i, result);
+}
+
+// ---- cadence_load_store_vh.h: the VersionHistories blob to store for every routed task --------------------------
+// one lane per task, load_store_kernel's launch: the decision, the blob's length from the branch table's token
+// lengths and item counts (nothing is walked), the row; the length goes to blob_off[i] for the scan, the
+// generated mark to the work buffer
+__global__ void __launch_bounds__(kBlock) load_store_vh_size_kernel(Ctx c, StoreIn a, ReplayAfter after, crr_vh_blob_row* rows,
+                                                                    int64_t* lens, int64_t* generated) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n_tasks) return;
+  const uint64_t len = vh_size_task(c, a, after, i, rows);
+  lens[i] = (int64_t)len;
+  generated[i] = len != 0;
+}
+
+// output-stationary: lane i owns bytes [16 i, 16 i + 16) of `out` and stores them as one dwordx4, whatever blobs
+// they belong to (load_decode.h's vh_emit_chunk); no LDS, no blob-size limit, and no store whose address depends
+// on anything but the lane's index
+__global__ void __launch_bounds__(kBlock) load_store_vh_emit_kernel(Ctx c, StoreIn a, ReplayAfter after, const uint64_t* blob_off,
+                                                                    uint64_t n_bytes, uint64_t n_chunks, ulonglong2* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_chunks) return;
+  uint64_t lo, hi;
+  vh_emit_chunk(c, a, after, blob_off, n_bytes, i, lo, hi);
+  out[i] = make_ulonglong2(lo, hi);
 }
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
@@ -520,18 +548,18 @@ int crr_load_ndc_run(const crr_state_batch* in, const void* scratch, size_t scra
   return (int)hipGetLastError();
 }
 
-int crr_load_store_checksums(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
-                             const crr_load_summary* summary_host, const crr_repl_task* tasks,
-                             const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
-                             const crr_ndc_route* routes, const crr_load_branches* branches,
-                             const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
-                             const crr_outputs* replay_out, const uint32_t* position, crr_store_row* result,
-                             void* stream) {
+// the read-only arguments crr_load_store_checksums and the two calls of cadence_load_store_vh.h share, checked
+// and packed for the kernels: 0, or -1 on an invalid argument
+static int store_setup(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                       const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                       const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                       const crr_ndc_route* routes, const crr_load_branches* branches,
+                       const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
+                       const crr_outputs* replay_out, const uint32_t* position, Ctx& c, StoreIn& a, ReplayAfter& after) {
   if (!in || !summary_host || !ndc_plan_host || ndc_plan_host->err != 0) return -1;
   const crr_load_ndc_sizes& P = *ndc_plan_host;
   if (in->n_blobs != summary_host->n_blobs || in->n_wf != summary_host->n_wf || P.n_wf != in->n_wf) return -1;   // not the planned batch
   if (n_tasks > P.n_tasks) return -1;
-  Ctx c;
   if (in->n_wf) {
     if (!plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
     if (in->n_blobs && (!in->bytes || !in->blob_off)) return -1;
@@ -544,27 +572,22 @@ int crr_load_store_checksums(const crr_state_batch* in, const void* scratch, siz
     if (replay_in->n_wf && (!replay_in->wf || !replay_out->exec)) return -1;
     if (replay_in->stride == 0 || ((replay_in->flags & CRR_IN_WAVE_TAIL) && replay_in->wave_begin > replay_in->n_wf)) return -1;
   }
+  memset(&a, 0, sizeof a);
+  memset(&after, 0, sizeof after);
   if (n_tasks) {
-    if (!tasks || !last_events || !results || !routes || !result || !branches) return -1;
+    if (!tasks || !last_events || !results || !routes || !branches) return -1;
     if (in->n_wf && (!branches->branch_begin || !branches->current)) return -1;
     if (P.n_branches && (!branches->branches || !branches->tokens)) return -1;
     if (P.n_items && !branches->items) return -1;
+    a.br = *branches;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
-  if (n_tasks == 0) return 0;
-  StoreIn a;
   a.tasks = tasks;
   a.last = last_events;
   a.results = results;
   a.routes = routes;
-  a.br = *branches;
   a.n_branches = P.n_branches;
   a.n_items = P.n_items;
   a.n_tasks = n_tasks;
-  ReplayAfter after;
-  memset(&after, 0, sizeof after);
   after.have = replay_in != nullptr;
   if (replay_in) {
     after.wf = replay_in->wf;
@@ -574,7 +597,119 @@ int crr_load_store_checksums(const crr_state_batch* in, const void* scratch, siz
     after.stride = replay_in->stride;
     after.wave_begin = (replay_in->flags & CRR_IN_WAVE_TAIL) ? replay_in->wave_begin : replay_in->n_wf;
   }
+  return 0;
+}
+
+int crr_load_store_checksums(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                             const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                             const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                             const crr_ndc_route* routes, const crr_load_branches* branches,
+                             const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
+                             const crr_outputs* replay_out, const uint32_t* position, crr_store_row* result,
+                             void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  if (store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                  ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (n_tasks && !result) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_tasks == 0) return 0;
   hipLaunchKernelGGL(load_store_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, a, after, result);
+  return (int)hipGetLastError();
+}
+
+// the plan's work buffer: the generated marks [n_tasks + 1] (scanned to their count), then the two totals
+struct VhLayout {
+  uint64_t marks, totals, end;
+};
+static VhLayout carve_vh(uint32_t n_tasks) {
+  VhLayout L;
+  uint64_t o = 0;
+  L.marks = o;   o = align16(o + ((uint64_t)n_tasks + 1) * sizeof(int64_t));
+  L.totals = o;  o = align16(o + 2 * sizeof(uint64_t));
+  L.end = o;
+  return L;
+}
+
+size_t crr_load_store_vh_scratch_bytes(uint32_t n_tasks) { return (size_t)carve_vh(n_tasks).end; }
+
+int crr_load_store_vh_plan(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                           const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                           const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                           const crr_ndc_route* routes, const crr_load_branches* branches,
+                           const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
+                           const crr_outputs* replay_out, const uint32_t* position, crr_vh_blob_row* rows,
+                           uint64_t* blob_off, void* work, size_t work_bytes, crr_vh_blob_sizes* plan, void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  if (!plan || store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                           ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (n_tasks && (!rows || !blob_off || !work || ((uintptr_t)work & 15u) || ((uintptr_t)blob_off & 7u))) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  const VhLayout L = carve_vh(n_tasks);
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  plan->work_needed = L.end;
+  hipError_t e;
+  if (n_tasks == 0) {
+    if (blob_off && (e = hipMemsetAsync(blob_off, 0, sizeof(uint64_t), s)) != hipSuccess) return (int)e;
+    return 0;
+  }
+  if (L.end > work_bytes) {
+    plan->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    return 0;
+  }
+  int64_t* marks = reinterpret_cast<int64_t*>(static_cast<uint8_t*>(work) + L.marks);
+  uint64_t* totals = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(work) + L.totals);
+  int64_t* lens = reinterpret_cast<int64_t*>(blob_off);
+  hipLaunchKernelGGL(load_store_vh_size_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, a, after, rows, lens, marks);
+  hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, lens, n_tasks, 1, totals);
+  hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, marks, n_tasks, 1, totals + 1);
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[2];
+  if ((e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  plan->n_bytes = h[0];
+  plan->n_generated = h[1];
+  return 0;
+}
+
+int crr_load_store_vh_run(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                          const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                          const crr_last_event* last_events, const crr_ndc_result* results, const crr_ndc_route* routes,
+                          const crr_load_branches* branches, const crr_load_ndc_sizes* ndc_plan_host,
+                          const crr_inputs* replay_in, const crr_outputs* replay_out, const uint32_t* position,
+                          const crr_vh_blob_row* rows, const uint64_t* blob_off, const crr_vh_blob_sizes* plan_host,
+                          uint8_t* out, size_t out_capacity, void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  if (!plan_host || plan_host->err != 0) return -1;
+  const uint32_t n_tasks = plan_host->n_tasks;
+  if (store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                  ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (n_tasks && (!rows || !blob_off)) return -1;
+  if (n_tasks == 0 && plan_host->n_bytes != 0) return -1;
+  const uint64_t padded = align16(plan_host->n_bytes);
+  if (padded < plan_host->n_bytes || (uint64_t)out_capacity < padded) return -1;
+  if (padded && (!out || ((uintptr_t)out & 15u))) return -1;
+  const uint64_t n_chunks = padded / 16, blocks = (n_chunks + kBlock - 1) / kBlock;
+  if (blocks > 0x7FFFFFFFull) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_chunks == 0) return 0;
+  hipLaunchKernelGGL(load_store_vh_emit_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, c, a, after, blob_off,
+                     plan_host->n_bytes, n_chunks, reinterpret_cast<ulonglong2*>(out));
   return (int)hipGetLastError();
 }
 

@@ -4,7 +4,8 @@
 // prefix scans between them, over a scratch laid out exactly like the device's.
 // crr_load_states_verify_host (include/cadence_load_verify.h) runs the same load, then load_decode.h's verify_wf;
 // crr_load_branches_host (include/cadence_load_ndc.h) the same load, then its branch walk;
-// crr_load_store_checksums_host (include/cadence_load_store.h) both, then load_decode.h's store_task per task.
+// crr_load_store_checksums_host (include/cadence_load_store.h) both, then load_decode.h's store_task per task;
+// crr_load_store_vh_host (include/cadence_load_store_vh.h) the same, then its sizes and its sequential blob writer.
 #include <stdlib.h>
 
 #include <thread>
@@ -211,6 +212,82 @@ extern "C" int crr_load_store_checksums_host(const crr_state_batch* in, const cr
   free(k.s);
   free(c.s);
   return ok ? 0 : -2;
+}
+
+// the VersionHistories blob to store for routed tasks (include/cadence_load_store_vh.h): the same load, branch walk
+// and decision, the lengths scanned serially, then load_decode.h's sequential writer per generated task
+extern "C" int crr_load_store_vh_host(const crr_state_batch* in, const crr_repl_task* tasks,
+                                      const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                                      const crr_ndc_route* routes, const crr_load_image* after, crr_vh_blob_row* rows,
+                                      uint64_t* blob_off, uint8_t* out, size_t out_capacity, crr_vh_blob_sizes* plan,
+                                      int threads) {
+  if (!in || !plan || (n_tasks && (!tasks || !last_events || !results || !routes))) return -1;
+  if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
+  NdcWork k;
+  if (count_branches(c, threads, k) != 0) {
+    free(c.s);
+    return -2;
+  }
+  StoreIn a;
+  a.tasks = tasks;
+  a.last = last_events;
+  a.results = results;
+  a.routes = routes;
+  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
+  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
+  a.n_tasks = n_tasks;
+  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
+  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
+  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
+  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
+  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
+  crr_vh_blob_row* my_rows = static_cast<crr_vh_blob_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_vh_blob_row)));
+  uint64_t* my_off = static_cast<uint64_t*>(calloc((size_t)n_tasks + 1, sizeof(uint64_t)));
+  int ret = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current && my_rows && my_off ? 0 : -2;
+  if (ret == 0) {
+    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
+    const ImageAfter img = {after, n_wf};
+    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { my_off[i] = vh_size_task(c, a, img, i, my_rows); });
+    uint64_t run = 0, generated = 0;
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+      const uint64_t len = my_off[i];
+      my_off[i] = run;
+      run += len;
+      generated += len != 0;
+    }
+    my_off[n_tasks] = run;
+    memset(plan, 0, sizeof *plan);
+    plan->n_tasks = n_tasks;
+    plan->n_generated = generated;
+    plan->n_bytes = run;
+    const uint64_t padded = align16(run);
+    if (out && (uint64_t)out_capacity < padded) {
+      ret = -1;   // nothing written
+    } else {
+      if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_vh_blob_row));
+      if (blob_off) memcpy(blob_off, my_off, ((size_t)n_tasks + 1) * sizeof(uint64_t));
+      if (out) {
+        parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) {
+          const uint64_t len = my_off[i + 1] - my_off[i];
+          if (len == 0) return;
+          StoreDecision D;
+          store_decide(c, a, img, i, D);
+          ByteSink K = {out + my_off[i], len, 0};
+          if (!D.generated() || !vh_blob_write(K, c, a, D) || K.len != len) memset(out + my_off[i], 0, (size_t)len);
+        });
+        if (padded > run) memset(out + run, 0, (size_t)(padded - run));
+      }
+    }
+  }
+  free(my_rows), free(my_off);
+  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
+  free(k.s);
+  free(c.s);
+  return ret;
 }
 
 extern "C" int crr_load_states_verify_host(const crr_state_batch* in, const crr_stored_checksum* stored,

@@ -467,6 +467,8 @@ def _host_lib():
         L.crr_load_branches_host.restype = ctypes.c_int
         L.crr_load_store_checksums_host.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_int]
         L.crr_load_store_checksums_host.restype = ctypes.c_int
+        L.crr_load_store_vh_host.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_int]
+        L.crr_load_store_vh_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -624,6 +626,36 @@ def store_checksums_host(sbs: StateBlobSet, tasks, last_events, results, routes,
     return out
 
 
+# ---- the VersionHistories blob to store with it (include/cadence_load_store_vh.h) -------------------------------
+def store_version_histories_host(sbs: StateBlobSet, tasks, last_events, results, routes, after: Optional[LoadedStates] = None,
+                                 threads: int = 1):
+    """The thriftrw ``VersionHistories`` DataBlob to store with each task's state once the task is committed (field
+    122 of the execution blob), by the host restatement (``crr_load_store_vh_host``), arguments as
+    ``store_checksums_host``: ``(rows abi.VH_BLOB_ROW[n], blob_off uint64[n + 1], bytes uint8[blob_off[n]])`` -- task
+    k's blob is ``bytes[blob_off[k]:blob_off[k + 1]]``, empty unless its outcome is ``APPLIED`` or ``BACKFILLED``."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
+    img, _keep = _after_image(after, sbs.n_wf)
+    n = int(tasks.shape[0])
+    P = abi.CVhBlobSizes()
+
+    def ptr(a):
+        return a.ctypes.data if a.size else None
+
+    def call(rows, off, out):
+        rc = L.crr_load_store_vh_host(ctypes.byref(c), ptr(tasks), ptr(last), n, ptr(results), ptr(routes),
+                                      ctypes.byref(img) if img is not None else None, rows, off, out[0], out[1],
+                                      ctypes.byref(P), threads)
+        if rc != 0:
+            raise RuntimeError(f"crr_load_store_vh_host failed: {rc}")
+    call(None, None, (None, 0))   # sizes
+    rows, off = np.zeros(n, abi.VH_BLOB_ROW), np.zeros(n + 1, np.uint64)
+    out = np.zeros((int(P.n_bytes) + 15) // 16 * 16, np.uint8)
+    call(ptr(rows), off.ctypes.data, (ptr(out), out.size))
+    return rows, off, out[:int(P.n_bytes)].copy()
+
+
 def apply_mask(routes: np.ndarray, tasks: Optional[np.ndarray] = None, n_wf: Optional[int] = None) -> np.ndarray:
     """The workflows whose task is to be replayed onto the placed rows (``ROUTE_APPLY_CURRENT``), as
     ``LoadedImage.resumable(mask=...)`` takes them (canonical workflow order; ``replication.BlobReplication``'s
@@ -695,6 +727,12 @@ class StateLoader:
         L.crr_load_ndc_run.restype = ctypes.c_int
         L.crr_load_store_checksums.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32] + [vp] * 9
         L.crr_load_store_checksums.restype = ctypes.c_int
+        L.crr_load_store_vh_scratch_bytes.argtypes = [ctypes.c_uint32]
+        L.crr_load_store_vh_scratch_bytes.restype = ctypes.c_size_t
+        L.crr_load_store_vh_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32] + [vp] * 10 + [ctypes.c_size_t, vp, vp]
+        L.crr_load_store_vh_plan.restype = ctypes.c_int
+        L.crr_load_store_vh_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 11 + [ctypes.c_size_t, vp]
+        L.crr_load_store_vh_run.restype = ctypes.c_int
         self.last_ndc = None
         self.scratch = None
         self.scratch_bytes = 0
@@ -861,25 +899,20 @@ class StateLoader:
                 host("out_items", abi.VH_ITEM, int(br.plan.n_out_items)))
 
     # ---- include/cadence_load_store.h ----------------------------------------------------------------------
-    def store_checksums(self, ds: DeviceStates, tasks, last_events, db=None, on_device: bool = False, perm=None):
-        """The checksum to store with each task's state once the task is committed (``crr_load_store_checksums``),
-        for the ``tasks`` the last ``ndc_prepare`` decided against the last plan's states (``self.last_ndc``: its
-        decisions, routes and branch table stay on the device): ``abi.STORE_ROW`` per task.  ``last_events``:
-        ``abi.LAST_EVENT`` per task.  ``db``: the resumed batch (an ``engine.DeviceBatch``) after its replay was
-        enqueued, for the tasks routed to the current branch; the position map is the inverse of ``perm`` (default:
-        the batch's own, as in ``place``).  Enqueued on the current stream; ``on_device``: the rows as a device byte
-        tensor, nothing copied back."""
+    def _store_args(self, ds: DeviceStates, tasks, last_events, db, perm, what: str):
+        """The read-only arguments ``crr_load_store_checksums`` and the calls of cadence_load_store_vh.h share, for
+        the tasks the last ``ndc_prepare`` decided: (n, the tensors to keep alive, the arguments up to and including
+        ``last_events``, the ones from ``results`` through ``position``)."""
         from .engine import _dev_bytes
         if self.last_ndc is None:
-            raise RuntimeError("store_checksums: no ndc_prepare to take the decisions from")
+            raise RuntimeError(f"{what}: no ndc_prepare to take the decisions from")
         torch, dev = self.torch, self.engine.dev
         br, out = self.last_ndc
         tasks, last = _task_arrays(tasks, last_events)
         n, n_wf = int(tasks.shape[0]), int(ds.c.n_wf)
         if n > int(br.plan.n_tasks):
             raise ValueError(f"{n} tasks, {int(br.plan.n_tasks)} decided")
-        T = {"tasks": _dev_bytes(torch, tasks, dev), "last": _dev_bytes(torch, last, dev),
-             "rows": torch.empty(max(n, 1) * abi.STORE_ROW.itemsize, dtype=torch.uint8, device=dev)}
+        T = {"tasks": _dev_bytes(torch, tasks, dev), "last": _dev_bytes(torch, last, dev)}
         if db is not None and perm is None:
             perm = db.batch.perm
         if db is not None and perm is not None:
@@ -891,14 +924,89 @@ class StateLoader:
 
         def ptr(t):
             return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-        rc = self.lib.crr_load_store_checksums(
-            ctypes.byref(ds.c), ptr(self.scratch), ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
-            ptr(T["tasks"]), ptr(T["last"]), n, ptr(out["results"]), ptr(out["routes"]), ctypes.byref(br.c), ctypes.byref(br.plan),
-            ctypes.byref(db.c_in) if db is not None else None, ctypes.byref(db.c_out) if db is not None else None,
-            ptr(T.get("position")), ptr(T["rows"]), self._stream())
+        head = (ctypes.byref(ds.c), ptr(self.scratch), ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
+                ptr(T["tasks"]), ptr(T["last"]))
+        tail = (ptr(out["results"]), ptr(out["routes"]), ctypes.byref(br.c), ctypes.byref(br.plan),
+                ctypes.byref(db.c_in) if db is not None else None, ctypes.byref(db.c_out) if db is not None else None,
+                ptr(T.get("position")))
+        return n, T, head, tail
+
+    def store_checksums(self, ds: DeviceStates, tasks, last_events, db=None, on_device: bool = False, perm=None):
+        """The checksum to store with each task's state once the task is committed (``crr_load_store_checksums``),
+        for the ``tasks`` the last ``ndc_prepare`` decided against the last plan's states (``self.last_ndc``: its
+        decisions, routes and branch table stay on the device): ``abi.STORE_ROW`` per task.  ``last_events``:
+        ``abi.LAST_EVENT`` per task.  ``db``: the resumed batch (an ``engine.DeviceBatch``) after its replay was
+        enqueued, for the tasks routed to the current branch; the position map is the inverse of ``perm`` (default:
+        the batch's own, as in ``place``).  Enqueued on the current stream; ``on_device``: the rows as a device byte
+        tensor, nothing copied back."""
+        n, T, head, tail = self._store_args(ds, tasks, last_events, db, perm, "store_checksums")
+        T["rows"] = self.torch.empty(max(n, 1) * abi.STORE_ROW.itemsize, dtype=self.torch.uint8, device=self.engine.dev)
+        rc = self.lib.crr_load_store_checksums(*head, n, *tail, ctypes.c_void_p(T["rows"].data_ptr()), self._stream())
         if rc != 0:
             raise RuntimeError(f"crr_load_store_checksums failed: {rc}")
         self.last_store = T   # alive until the stream has run the kernel
         if on_device:
             return T["rows"]
         return T["rows"][:n * abi.STORE_ROW.itemsize].cpu().numpy().view(abi.STORE_ROW).copy()
+
+    # ---- include/cadence_load_store_vh.h -------------------------------------------------------------------
+    def store_version_histories_plan(self, ds: DeviceStates, tasks, last_events, db=None, perm=None) -> "VhBlobPlan":
+        """Decide and size (``crr_load_store_vh_plan``, one synchronisation): the rows and offsets stay on the device,
+        ``plan.sizes.n_bytes`` is what ``store_version_histories_run`` will write, rounded up to 16."""
+        n, T, head, tail = self._store_args(ds, tasks, last_events, db, perm, "store_version_histories")
+        torch, dev = self.torch, self.engine.dev
+        work_bytes = int(self.lib.crr_load_store_vh_scratch_bytes(n))
+        T["rows"] = torch.empty(max(n, 1) * abi.VH_BLOB_ROW.itemsize, dtype=torch.uint8, device=dev)
+        T["blob_off"] = torch.empty((n + 1) * 8, dtype=torch.uint8, device=dev)
+        T["work"] = torch.empty(work_bytes + 16, dtype=torch.uint8, device=dev)
+        P = abi.CVhBlobSizes()
+        rc = self.lib.crr_load_store_vh_plan(*head, n, *tail, ctypes.c_void_p(T["rows"].data_ptr()),
+                                             ctypes.c_void_p(T["blob_off"].data_ptr()), ctypes.c_void_p(T["work"].data_ptr()),
+                                             ctypes.c_size_t(work_bytes), ctypes.byref(P), self._stream())
+        if rc != 0 or P.err != 0:
+            raise RuntimeError(f"crr_load_store_vh_plan failed: {rc} (err {P.err})")
+        return VhBlobPlan(n, P, T, head, tail)
+
+    def store_version_histories_run(self, plan: "VhBlobPlan", out=None, capacity: Optional[int] = None):
+        """Emit the planned blobs (``crr_load_store_vh_run``, enqueued on the current stream) into ``out``, a device
+        uint8 tensor whose start is 16-byte aligned (default: one of exactly the padded size), of which ``capacity``
+        bytes (default: all) may be written; returns ``out``.  Too small a capacity raises and launches nothing."""
+        padded = (int(plan.sizes.n_bytes) + 15) // 16 * 16
+        if out is None:
+            out = self.torch.empty(max(padded, 16), dtype=self.torch.uint8, device=self.engine.dev)
+        capacity = int(out.numel() if capacity is None else capacity)
+        T = plan.tensors
+        rc = self.lib.crr_load_store_vh_run(*plan.head, *plan.tail, ctypes.c_void_p(T["rows"].data_ptr()),
+                                            ctypes.c_void_p(T["blob_off"].data_ptr()), ctypes.byref(plan.sizes),
+                                            ctypes.c_void_p(out.data_ptr()), ctypes.c_size_t(capacity), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_store_vh_run failed: {rc}")
+        T["out"] = out
+        self.last_store_vh = plan   # alive until the stream has run the kernel
+        return out
+
+    def store_version_histories(self, ds: DeviceStates, tasks, last_events, db=None, perm=None, on_device: bool = False):
+        """The thriftrw ``VersionHistories`` DataBlob to store with each task's state once the task is committed
+        (field 122 of the execution blob), generated on the device for the tasks the last ``ndc_prepare`` decided;
+        arguments as ``store_checksums``, whose outcome and status every row repeats:
+        ``(rows abi.VH_BLOB_ROW[n], blob_off uint64[n + 1], bytes uint8[blob_off[n]])`` -- task k's blob is
+        ``bytes[blob_off[k]:blob_off[k + 1]]``, empty unless its outcome is ``APPLIED`` or ``BACKFILLED``.
+        ``on_device``: the three as device byte tensors (``bytes`` padded to 16 with zeros), nothing more copied back."""
+        plan = self.store_version_histories_plan(ds, tasks, last_events, db=db, perm=perm)
+        out = self.store_version_histories_run(plan)
+        T, n = plan.tensors, plan.n
+        if on_device:
+            return T["rows"], T["blob_off"], out
+        return (T["rows"][:n * abi.VH_BLOB_ROW.itemsize].cpu().numpy().view(abi.VH_BLOB_ROW).copy(),
+                T["blob_off"].cpu().numpy().view(np.uint64).copy(), out[:int(plan.sizes.n_bytes)].cpu().numpy().copy())
+
+
+@dataclasses.dataclass
+class VhBlobPlan:
+    """A finished ``crr_load_store_vh_plan``: the host sizes, the device rows / offsets / work buffer and the
+    arguments of the call, which ``crr_load_store_vh_run`` takes again."""
+    n: int
+    sizes: abi.CVhBlobSizes
+    tensors: Dict[str, object]
+    head: tuple
+    tail: tuple

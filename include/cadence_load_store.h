@@ -38,7 +38,7 @@
  *
  * What stays on the host: tasks that fork a new branch (its token comes from ForkHistoryBranch, a persistence
  * write), the rebuild route, the active-side reapply of a backfill, continue-as-new's new run, and encoding the
- * updated VersionHistories and state blobs for the store.
+ * state blobs for the store (the updated VersionHistories blob is cadence_load_store_vh.h's).
  *
  * This header is an addition to ABI version 8: CRR_ABI_VERSION and every existing struct and entry point are
  * unchanged; crr_sizeof(27) / (28) report the two structs below.

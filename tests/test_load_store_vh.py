@@ -1,0 +1,296 @@
+"""The VersionHistories blob to store for routed replication tasks, by the host restatement (crr_load_store_vh_host,
+include/cadence_load_store_vh.h): the thriftrw DataBlob SerializeVersionHistories gives when
+CloseTransactionAsMutation commits a task applied to the current branch or backfilled onto another one.
+
+Expected bytes are persisted.encode_version_histories (the Python writer) over the histories the cases wrote into the
+blobs, changed by store_cases.add_or_update and by the hand-written or the oracle's vh rows (vh_blob_cases.py).  The
+blob is also checked against the checksum generated for the same task (its histories give that CRC), stored back as
+field 122 and loaded again, and written into a buffer of exactly its size between guard bytes.  A stand-alone program
+runs the same call under AddressSanitizer / UndefinedBehaviorSanitizer.
+"""
+import ctypes
+import functools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from cadence_amd import abi, persisted
+from cadence_amd.persisted import (load_branches_host, load_states_host, load_states_verify_host, store_checksums_host,
+                                   store_version_histories_host)
+
+import ndc_load_cases as nc
+import store_cases as sc
+import verify_cases as vc
+import vh_blob_cases as vb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+O = abi.StoreOutcome
+
+
+def _same_decision(rows: np.ndarray, want: np.ndarray, what=""):
+    for f in ("outcome", "status"):
+        bad = np.nonzero(rows[f] != want[f])[0]
+        assert bad.size == 0, f"{what} {f}: tasks {bad[:5]}: {rows[f][bad[:5]]} vs {want[f][bad[:5]]}"
+
+
+@pytest.mark.parametrize("with_after", [True, False])
+def test_hand_states_every_outcome_and_every_branch_shape(with_after):
+    c = sc.hand_case()
+    want = c.want if with_after else c.want_without
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes, c.after if with_after else None)
+    _same_decision(rows, want, "hand case")
+    if with_after:
+        assert set(int(x) for x in rows["outcome"]) == set(int(x) for x in O)
+    else:
+        assert not (rows["outcome"] == O.APPLIED).any() and (rows["outcome"] == O.NOT_RESUMED).sum() >= 6
+    expected = vb.hand_expected(c, want)
+    vb.assert_blobs(rows, off, data, expected, "hand case")
+    # the header's closed form
+    for k, e in enumerate(expected):
+        if e is not None:
+            assert int(rows[k]["len"]) == len(e) == vb.blob_length(vb.hand_histories(c, k, int(want[k]["outcome"]))[1])
+    # a 300-byte token, an absent one, an empty one, absent items, and all three AddOrUpdateItem modes
+    assert {"token 300", "token absent", "token empty", "items absent", "takes", "updates", "appends"} <= vb.hand_modes(c, want)
+    # tasks are independent: any order, any subset, any number of threads
+    order = np.random.default_rng(2).permutation(c.tasks.shape[0])[:20]
+    r2, o2, d2 = store_version_histories_host(c.sbs, c.tasks[order], c.last_events[order], c.results[order], c.routes[order],
+                                              c.after if with_after else None, threads=3)
+    vb.assert_blobs(r2, o2, d2, [expected[k] for k in order], "subset")
+
+
+def test_the_header_example_is_437_bytes():
+    hs = [(b"abc", [(1, 1), (2, 2)]), (b"", []), (bytes(300), [(5, 5)])]
+    assert len(vb.expected_blob(1, hs)) == vb.blob_length(hs) == 437
+
+
+def test_task_case_with_the_expected_routes():
+    c = sc.routed_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    _same_decision(rows, c.want, "task_case")
+    vb.assert_blobs(rows, off, data, vb.routed_expected(c), "task_case")
+    assert (rows["outcome"] == O.BACKFILLED).sum() >= 20 and (rows["outcome"] == O.NOT_RESUMED).sum() >= 60
+    r4, o4, d4 = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes, threads=4)
+    assert (r4.tobytes(), o4.tobytes(), d4.tobytes()) == (rows.tobytes(), off.tobytes(), data.tobytes())
+
+
+def test_large_and_seam_cases_on_the_host():
+    for case, seams in ((vb.large_case(), False), (vb.seam_case(), True)):
+        (sbs, tasks, last, results, routes), want = case
+        rows, off, data = store_version_histories_host(sbs, tasks, last, results, routes)
+        vb.assert_blobs(rows, off, data, want)
+        if seams:
+            vb.assert_seams(rows, off)
+        else:
+            assert int(rows["len"].max()) > 5000
+
+
+def _payload_crc(ex, live_rows, sticky: str, blob: bytes) -> int:
+    current, hs = vb.parse(blob)
+    return vc.crc(sc.payload_of_rows(ex, live_rows, sticky, current, hs))
+
+
+def test_the_blob_is_what_the_generated_checksum_covers():
+    """For every generated task the blob's (current, histories), put into the checksum payload with the state's other
+    fields, give the CRC crr_load_store_checksums_host generated for that task."""
+    c = sc.hand_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes, c.after)
+    sums = store_checksums_host(c.sbs, c.tasks, c.last_events, c.results, c.routes, c.after)
+    stored = load_states_host(c.sbs)
+    blobs, n = vb.blobs_of(rows, off, data), 0
+    for k in range(rows.shape[0]):
+        assert (int(rows[k]["outcome"]), int(rows[k]["status"])) == (int(sums[k]["outcome"]), int(sums[k]["status"]))
+        if int(rows[k]["outcome"]) not in vb.GENERATED:
+            continue
+        w = int(c.tasks[k]["wf"])
+        if int(rows[k]["outcome"]) == O.APPLIED:
+            got = _payload_crc(c.after.exec[w], sc.rows_of(c.after, w), "", blobs[k])
+        else:
+            got = _payload_crc(stored.exec[w], sc.rows_of(stored, w), sc.HAND_STATES[w]["sticky"], blobs[k])
+        assert got == int(sums[k]["value"]), k
+        n += 1
+    assert n >= 10
+    # the routed case: no sticky names, the scalars as loaded
+    c = sc.routed_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    sums = store_checksums_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    stored = load_states_host(c.sbs)
+    blobs = vb.blobs_of(rows, off, data)
+    gen = np.nonzero(rows["len"] > 0)[0]
+    assert gen.size >= 20 and (rows["outcome"] == sums["outcome"]).all() and (rows["status"] == sums["status"]).all()
+    for k in gen:
+        w = int(c.tasks[k]["wf"])
+        assert _payload_crc(stored.exec[w], sc.rows_of(stored, w), "", blobs[k]) == int(sums[k]["value"]), k
+
+
+def _round_trip(sbs, tasks, rows, blobs, sums, histories_of):
+    """Every generated task's state written back with the blob as field 122 and the checksum as stored: the branch
+    table of the new states is the expected one and Load verifies them."""
+    before = nc.workflows_of(sbs)
+    wfs, stored, want = [], [], []
+    for k in np.nonzero(rows["len"] > 0)[0]:
+        wfs.append(vb.with_vh_blob(before[int(tasks[k]["wf"])], blobs[k]))
+        stored.append(vb.stored_of(sums[k]["value"]))
+        want.append(nc.expected_of(*histories_of(int(k))))
+    new = persisted.build_blob_set(wfs)
+    assert nc.table_of(new, load_branches_host(new)) == want
+    v = load_states_verify_host(new, persisted.stored_checksums(stored))
+    assert (v["outcome"] == abi.VerifyOutcome.MATCH).all()
+    return len(wfs)
+
+
+def test_round_trip_backfilled_blobs_load_and_verify():
+    c = sc.hand_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    sums = store_checksums_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    n = _round_trip(c.sbs, c.tasks, rows, vb.blobs_of(rows, off, data), sums,
+                    lambda k: vb.hand_histories(c, k, int(O.BACKFILLED)))
+    assert n >= 7
+    c = sc.routed_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    sums = store_checksums_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    assert _round_trip(c.sbs, c.tasks, rows, vb.blobs_of(rows, off, data), sums, lambda k: vb.routed_histories(c, k)) >= 20
+
+
+@functools.lru_cache(maxsize=None)
+def _replayed_host():
+    rc = sc.replayed_case()
+    res, routes = sc.decided(rc)
+    resumed = persisted.apply_mask(routes, rc.tasks, rc.sbs.n_wf)
+    after = rc.one_r.to_loaded(rc.one_b, mask=resumed)
+    got = store_version_histories_host(rc.sbs, rc.tasks, rc.last_events, res, routes, after)
+    sums = store_checksums_host(rc.sbs, rc.tasks, rc.last_events, res, routes, after)
+    return rc, res, routes, resumed, after, got, sums
+
+
+def test_replayed_states_applied_and_backfilled():
+    rc, res, routes, resumed, after, (rows, off, data), sums = _replayed_host()
+    want = sc.expected_replayed(rc, routes, res, resumed, after)
+    _same_decision(rows, want, "replayed case")
+    assert (rows["outcome"] == sums["outcome"]).all() and (rows["status"] == sums["status"]).all()
+    vb.assert_blobs(rows, off, data, vb.replayed_expected(rc, want, after), "replayed case")
+    applied, two = rows["outcome"] == O.APPLIED, rc.two_branch[rc.tasks["wf"]]
+    assert (applied & two).sum() >= 15 and (applied & ~two).sum() >= 15 and (rows["outcome"] == O.BACKFILLED).sum() >= 5
+
+
+def test_round_trip_applied_blobs_load_and_verify():
+    """The states after their task as the store would hold them (the whole histories' replay persisted), their
+    field 122 replaced by the generated blob and the generated checksum stored: they load to the expected table and
+    verify."""
+    rc, _res, _routes, _resumed, after, (rows, off, data), sums = _replayed_host()
+    blobs = vb.blobs_of(rows, off, data)
+    applied, by_wf = np.zeros(rc.sbs.n_wf, bool), {}
+    for k in np.nonzero(rows["outcome"] == O.APPLIED)[0]:
+        applied[int(rc.tasks[k]["wf"])] = True
+        by_wf[int(rc.tasks[k]["wf"])] = int(k)
+    assert applied.sum() >= 30
+    stored_states = nc.workflows_of(sc.reencoded_applied(rc, applied))
+    wfs, stored, want = [], [], []
+    for w in np.nonzero(applied)[0]:
+        k = by_wf[int(w)]
+        wfs.append(vb.with_vh_blob(stored_states[int(w)], blobs[k]))
+        stored.append(vb.stored_of(sums[k]["value"]))
+        want.append(nc.expected_of(*sc.histories_of(rc, int(w), vb._vh_rows(after, int(w)))))
+    new = persisted.build_blob_set(wfs)
+    assert nc.table_of(new, load_branches_host(new)) == want
+    assert (load_states_verify_host(new, persisted.stored_checksums(stored))["outcome"] == abi.VerifyOutcome.MATCH).all()
+
+
+def _raw_call(c, out_bytes: int, capacity: int, guard: int = 64):
+    """crr_load_store_vh_host into ``out_bytes`` bytes between two guards: (rc, sizes, the whole buffer, rows, offsets)."""
+    host = persisted._host_lib()
+    cb = persisted._c_batch(c.sbs, lambda a: a.ctypes.data)
+    n = c.tasks.shape[0]
+    rows, off = np.full(n, 0x5A5A5A5A, np.uint32).repeat(4).view(abi.VH_BLOB_ROW), np.full(n + 1, 0x5A5A5A5A5A5A5A5A, np.uint64)
+    buf = np.full(guard + out_bytes + guard + 16, 0xA5, np.uint8)
+    start = guard + (-(buf.ctypes.data + guard)) % 16          # a 16-byte aligned start
+    P = abi.CVhBlobSizes()
+    rc = host.crr_load_store_vh_host(ctypes.byref(cb), c.tasks.ctypes.data, c.last_events.ctypes.data, n, c.results.ctypes.data,
+                                     c.routes.ctypes.data, None, rows.ctypes.data, off.ctypes.data, buf.ctypes.data + start,
+                                     capacity, ctypes.byref(P), 1)
+    return rc, P, buf, start, rows, off
+
+
+def test_bounds_exact_capacity_and_one_byte_short():
+    c = sc.hand_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    n_bytes = int(off[-1])
+    assert n_bytes % 16 != 0            # the padded tail is exercised
+    padded = (n_bytes + 15) // 16 * 16
+    rc, P, buf, start, r, o = _raw_call(c, padded, padded)
+    assert rc == 0 and int(P.n_bytes) == n_bytes and int(P.n_tasks) == c.tasks.shape[0] and int(P.err) == 0
+    assert int(P.n_generated) == int((rows["len"] > 0).sum())
+    assert (buf[:start] == 0xA5).all() and (buf[start + padded:] == 0xA5).all()
+    assert buf[start:start + n_bytes].tobytes() == data.tobytes() and (buf[start + n_bytes:start + padded] == 0).all()
+    assert r.tobytes() == rows.tobytes() and o.tobytes() == off.tobytes()
+    # one byte short: -1, nothing written, not the rows either
+    rc, P, buf, start, r, o = _raw_call(c, padded, padded - 1)
+    assert rc == -1 and (buf == 0xA5).all()
+    assert (r.view(np.uint32) == 0x5A5A5A5A).all() and (o == 0x5A5A5A5A5A5A5A5A).all()
+
+
+def test_empty_batch_and_no_tasks():
+    empty = persisted.build_blob_set([])
+    tasks = np.zeros(3, abi.REPL_TASK)
+    tasks["wf"] = [0, 5, 0xFFFFFFFF]
+    routes = np.zeros(3, abi.NDC_ROUTE)
+    routes["route"] = abi.ROUTE_APPLY_CURRENT
+    rows, off, data = store_version_histories_host(empty, tasks, np.zeros(3, abi.LAST_EVENT), np.zeros(3, abi.NDC_RESULT), routes)
+    assert rows.tolist() == [(0, int(O.NOT_LOADED), 0, 0)] * 3 and off.tolist() == [0, 0, 0, 0] and data.shape == (0,)
+    c = sc.hand_case()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks[:0], c.last_events[:0], c.results[:0], c.routes[:0], c.after)
+    assert rows.shape == (0,) and off.tolist() == [0] and data.shape == (0,)
+
+
+def test_header_pins_and_bad_arguments():
+    from cadence_amd import decode, engine
+    text = open(os.path.join(ROOT, "include", "cadence_load_store_vh.h")).read()
+    assert set(re.findall(r"\b(crr_load_\w+)\s*\(", text)) >= {"crr_load_store_vh_scratch_bytes", "crr_load_store_vh_plan",
+                                                               "crr_load_store_vh_run", "crr_load_store_vh_host"}
+    dev = ctypes.CDLL(engine.LIB_PATH)
+    for name in ("crr_load_store_vh_scratch_bytes", "crr_load_store_vh_plan", "crr_load_store_vh_run"):
+        assert hasattr(dev, name), name
+    assert hasattr(decode.lib(), "crr_load_store_vh_host")
+    dev.crr_abi_version.restype = ctypes.c_int
+    assert dev.crr_abi_version() == abi.ABI_VERSION == 8
+    abi.check_layout(dev)
+    assert dev.crr_sizeof(30) == abi.VH_BLOB_ROW.itemsize == 16 and dev.crr_sizeof(31) == ctypes.sizeof(abi.CVhBlobSizes) == 32
+    assert dev.crr_sizeof(29) == 0 and dev.crr_sizeof(32) == 0
+    dev.crr_load_store_vh_scratch_bytes.restype = ctypes.c_size_t
+    assert dev.crr_load_store_vh_scratch_bytes(0) % 16 == 0 and dev.crr_load_store_vh_scratch_bytes(1000) >= 8 * 1001 + 16
+    # invalid shapes: -1, as the sibling calls
+    vp = ctypes.c_void_p
+    S, N, P = abi.CLoadSummary(), abi.CLoadNdcSizes(), abi.CVhBlobSizes()
+    dev.crr_load_store_vh_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32] + [vp] * 10 + [ctypes.c_size_t, vp, vp]
+    assert dev.crr_load_store_vh_plan(None, None, 0, ctypes.byref(S), None, None, 0, None, None, None, ctypes.byref(N), None, None,
+                                      None, None, None, None, 0, ctypes.byref(P), None) == -1
+    dev.crr_load_store_vh_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 11 + [ctypes.c_size_t, vp]
+    assert dev.crr_load_store_vh_run(None, None, 0, ctypes.byref(S), None, None, None, None, None, ctypes.byref(N), None, None,
+                                     None, None, None, ctypes.byref(P), None, 0, None) == -1
+    host = persisted._host_lib()
+    c = sc.hand_case()
+    cb = persisted._c_batch(c.sbs, lambda a: a.ctypes.data)
+    args = [c.tasks.ctypes.data, c.last_events.ctypes.data, c.tasks.shape[0], c.results.ctypes.data, c.routes.ctypes.data, None,
+            None, None, None, 0, ctypes.byref(P), 1]
+    assert host.crr_load_store_vh_host(None, *args) == -1
+    for drop in (0, 1, 3, 4, 10):
+        bad = list(args)
+        bad[drop] = None
+        assert host.crr_load_store_vh_host(ctypes.byref(cb), *bad) == -1, drop
+    img = abi.CLoadImage()                                                    # an after-image without exec rows
+    bad = list(args)
+    bad[5] = ctypes.byref(img)
+    assert host.crr_load_store_vh_host(ctypes.byref(cb), *bad) == -1
+    assert host.crr_load_store_vh_host(ctypes.byref(cb), *args) == 0 and int(P.n_bytes) > 1000   # the sizing call
+
+
+def test_host_restatement_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "load_store_vh_asan")
+    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_store_vh_asan.cpp"),
+                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "no sanitizer report" in p.stdout
