@@ -5047,7 +5047,10 @@ __global__ void __launch_bounds__(kBlock) checksum_kernel(crr_inputs in, crr_out
   TokenWords TW;
   TW.issue(token_desc(wfp), R.token_src, in.arena, in.token_crc, w);
   u32 len = 0;
-  if (out.live_ids[0]) {  // the ID lists from the dense sidecar the replay wrote
+  // the ID lists from the dense sidecar: whoever wrote the rows of an OK workflow (a replay, the loader's
+  // placement, an upload of loaded states) wrote its slots too; a workflow that ended in an error has its
+  // counts in the exec row but no sidecar slots of this call
+  if (out.live_ids[0] && R.status == CRR_OK) {
     const SidecarIds ids{out.live_ids};
     checksums[w] = payload_crc(R, ids, G, TW, in.arena, crc_tables, &len);
   } else {                // ... or one field of each AoS row

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import abi
-from .flatten import HistoryBatch, fits_small_tier
+from .flatten import LOADED_ID, HistoryBatch, fits_small_tier
 from .result import ReplayResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -162,9 +162,14 @@ class ReplayEngine:
         co.scratch = T["scratch"].data_ptr()
         if live_ids:
             # the live-ID sidecar (crr_outputs.live_ids): one int64 per row slot of each pending map, written by the
-            # replay for every OK workflow and read by crr_checksum instead of the rows
+            # replay for every OK workflow and read by crr_checksum instead of the rows; loaded rows bring their
+            # IDs along, so the sidecar describes the rows before any launch too
             for t, name in enumerate(abi.ID_TABLES):
                 T["ids_" + name] = torch.zeros(max(batch.table_rows.get(name, 0), 1), dtype=torch.int64, device=dev)
+                if init_host is not None:
+                    ids = np.ascontiguousarray(init_host.tables[name][LOADED_ID[name]], dtype=np.int64)
+                    n = min(ids.size, T["ids_" + name].numel())
+                    T["ids_" + name][:n].copy_(torch.from_numpy(ids[:n]))
                 co.live_ids[t] = T["ids_" + name].data_ptr()
         if token_crc and batch.n_wf:
             # crr_inputs.token_crc: each start token's raw CRC, computed once the arena is in HBM (a token is

@@ -163,7 +163,9 @@ class PassiveReplication:
         torch.cuda.synchronize(eng.dev)
 
     def _state_keys(self):
-        return ["exec"] + ["out_" + name for name, *_ in abi.TABLES]
+        # the live-ID sidecar is part of the state: crr_checksum reads it in place of the rows' ID fields
+        ids = ["ids_" + name for name in abi.ID_TABLES if "ids_" + name in self.db.tensors]
+        return ["exec"] + ["out_" + name for name, *_ in abi.TABLES] + ids
 
     def restore(self, stream=None):
         torch = self.eng.torch

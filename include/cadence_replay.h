@@ -48,6 +48,7 @@ extern "C" {
  *    RefreshTasks' own task rows (task_cap), RefreshTasks' state effects without CRR_IN_EMIT_TASKS too,
  *    the fused digest (crr_inputs.digest_keys, crr_outputs.digest), crr_sizeof(13 / 14)
  * 6: the live-ID sidecar (crr_outputs.live_ids)
+ * 7: crr_inputs.token_crc
  * 8: the persisted mutable-state loader (cadence_load.h), crr_sizeof(15..19); added since, without a new
  *    version: the checksum verification of loaded states (cadence_load_verify.h), crr_sizeof(20 / 21); the branch
  *    and routing decisions for tasks against loaded states (cadence_load_ndc.h), crr_sizeof(22..26) and
@@ -515,7 +516,12 @@ typedef struct crr_outputs {
        crr_replay writes, for every workflow it finalises with status CRR_OK, the IDs of slots 0..n-1 (the
        checksum's ID lists: the live rows' IDs in ascending order), so a reader of the IDs alone -- crr_checksum
        (the Load verify path) -- reads 8 dense bytes per row instead of one cache line of each AoS row.  All
-       five set or none. */
+       five set or none.
+       Invariant: for every workflow whose exec row has status CRR_OK, slot i < n of each column holds the ID of
+       row slot i.  Whoever writes such rows keeps it: crr_replay, crr_load_states_place, and a host that
+       uploads loaded rows or restores a saved copy of the rows (it fills, or saves and restores, the columns
+       with them).  A workflow that crr_replay ends with an error gets its exec row and counts but no sidecar
+       slots, so its slots are unspecified and no reader may use them. */
     int64_t*             live_ids[5];
 } crr_outputs;
 
@@ -596,8 +602,9 @@ int crr_replay(const crr_inputs* in, const crr_outputs* out, void* stream);
 
 /* Recompute checksums of already-replayed rows (the Load verify path,
  * mutable_state_builder.go:334-348 -> checksum.go:45-54).  Writes checksums[n_wf].  With the live-ID
- * sidecar set (crr_outputs.live_ids, as the replay that wrote the rows left it) the ID lists are read from
- * it, else from the rows. */
+ * sidecar set (crr_outputs.live_ids, kept as its invariant there says) the ID lists of every workflow whose
+ * exec row has status CRR_OK are read from it; those of any other workflow, and of all of them without a
+ * sidecar, are read from the rows.  Both give the same value wherever the invariant holds. */
 int crr_checksum(const crr_inputs* in, const crr_outputs* out, uint32_t* checksums, void* stream);
 
 /* crr_inputs.token_crc: the raw CRC of every workflow's start token (in->arena at start_token_off /

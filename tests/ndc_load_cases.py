@@ -267,6 +267,20 @@ def task_case(n_states: int = 130, n_tasks: int = 400, seed: int = 3, big: bool 
     return TaskCase(sbs, loaded, states, tasks, np.array(items, abi.VH_ITEM), ndc_tasks, known)
 
 
+# task_case sizes past one element per thread of the loader's 1024-thread scans (per = ceil(n / 1024) consecutive
+# elements each, over the states' branch and item counts and over the tasks' rooms, blob lengths and marks):
+# (1300, 2500): states per = 2, threads from 650 up idle; tasks per = 3, 2500 = 833 * 3 + 1, so thread 833 holds
+#               one element and the threads behind it none
+# (1025, 1025): the first size with per = 2; thread 512 holds the one last element
+LARGE_CASES = ((1300, 2500), (1025, 1025))
+
+
+def written_table(case: TaskCase):
+    """``table_of``'s value for the branch table of ``case``'s states, from the values task_case wrote."""
+    return [expected_of(cur, [(b"token-%d-%d" % (w, b) if (w + b) % 5 else None, items) for b, items in enumerate(local)])
+            if case.loaded[w] else None for w, (cur, local) in enumerate(case.locals_)]
+
+
 def oracle_decisions(case: TaskCase):
     """``oracle.ndc_prepare`` on ``ndc.pack`` of the decided tasks: (indices of the decided tasks, batch, results,
     out items)."""

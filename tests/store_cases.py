@@ -222,8 +222,9 @@ def _written(w: int, local):
 
 
 @functools.lru_cache(maxsize=None)
-def routed_case() -> StoreCase:
-    case = nc.task_case()
+def routed_case(n_states: int = 130, n_tasks: int = 400, seed: int = 3, big: bool = True) -> StoreCase:
+    """ndc_load_cases.task_case of the same arguments with the expected decisions and the expected rows."""
+    case = nc.task_case(n_states, n_tasks, seed, big)
     results, routes, _new = nc.expected_routes(case)
     n = case.tasks.shape[0]
     last = np.array([last_event_of(case.tasks[k], k) for k in range(n)], abi.LAST_EVENT)
@@ -329,6 +330,13 @@ def replayed_case_of(hs, split_seed: int, second_every: int, shuffle_seed: int =
 @functools.lru_cache(maxsize=None)
 def replayed_case() -> ReplayedCase:
     return replayed_case_of(synth_mixed.mixed_histories(64, 81, multi_version=True), 82, 2)
+
+
+@functools.lru_cache(maxsize=None)
+def replayed_case_large() -> ReplayedCase:
+    """replayed_case's recipe over 1400 histories: 1400 states and 1366 tasks, so the loader's 1024-thread scans hold
+    more than one element per thread and APPLIED and BACKFILLED tasks lie past task 1024."""
+    return replayed_case_of(synth_mixed.mixed_histories(1400, 81, multi_version=True), 82, 2)
 
 
 def histories_of(rc: ReplayedCase, w: int, own_items):

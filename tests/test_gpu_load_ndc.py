@@ -72,8 +72,7 @@ def test_device_branch_table_equals_host(loader, decided):
     assert nc.table_of(sbs, dev) == want
 
 
-def test_results_equal_the_oracle_on_the_values_written(decided):
-    case, _ds, _table, results, _routes, out_items, out_begin = decided
+def _check_results(case, results, out_items, out_begin):
     want, _want_routes, want_items = nc.expected_routes(case)
     assert results.dtype == abi.NDC_RESULT and results.shape == want.shape
     for f in abi.NDC_RESULT.names:
@@ -94,8 +93,12 @@ def test_results_equal_the_oracle_on_the_values_written(decided):
     assert all(results[k].tobytes() == zero.tobytes() for k in np.nonzero(nd)[0])
 
 
-def test_routes_equal_the_restatement_and_the_known_answers(decided):
-    case, _ds, _table, _results, routes, _out, _ob = decided
+def test_results_equal_the_oracle_on_the_values_written(decided):
+    case, _ds, _table, results, _routes, out_items, out_begin = decided
+    _check_results(case, results, out_items, out_begin)
+
+
+def _check_routes(case, routes):
     _want, want, _items = nc.expected_routes(case)
     assert routes.dtype == abi.NDC_ROUTE
     for f in abi.NDC_ROUTE.names:
@@ -104,6 +107,36 @@ def test_routes_equal_the_restatement_and_the_known_answers(decided):
     assert set(int(r) for r in routes["route"]) == set(range(5))
     assert tuple(routes[case.known["no_rebuild"]]) == (abi.ROUTE_APPLY_CURRENT, 0, 0, 0, 0, 0)
     assert tuple(routes[case.known["rebuild"]]) == (abi.ROUTE_REBUILD, 0, 2, 0, 1, 12)
+
+
+def test_routes_equal_the_restatement_and_the_known_answers(decided):
+    case, _ds, _table, _results, routes, _out, _ob = decided
+    _check_routes(case, routes)
+
+
+@pytest.mark.parametrize("n_states,n_tasks", nc.LARGE_CASES)
+def test_more_than_one_element_per_scan_thread(loader, n_states, n_tasks):
+    """The branch table, the decisions, the routes and the new-branch room with more than 1024 states and tasks:
+    the loader's one-block scans then give each thread a chunk of several elements, a clipped last chunk and idle
+    threads behind it, and the second row of the states' scan starts at n_wf + 1 (ndc_load_cases.LARGE_CASES).
+
+    (1300, 2500): 3392 branches (the longest 600 items), 11 tasks not decided, routes NONE / APPLY_CURRENT /
+    NON_CURRENT / REBUILD / BAD_REQUEST 1346 / 521 / 233 / 388 / 12, 12323 items of new-branch room.
+    (1025, 1025): 2699 branches, 7 tasks not decided, routes 570 / 199 / 89 / 165 / 2, 4779 items of room."""
+    case = nc.task_case(n_states, n_tasks)
+    assert case.sbs.n_wf == n_states > 1024 and case.tasks.shape[0] == n_tasks > 1024
+    ds = loader.upload(case.sbs)
+    loader.plan(ds)
+    results, routes, out_items = loader.ndc_prepare(ds, case.tasks, case.incoming)
+    table, out_begin = loader.last_ndc[0].read(), loader.last_out_begin.copy()
+    host = load_branches_host(case.sbs)
+    _same_table(table, host, "with tasks")
+    assert host.branches.shape[0] > 2 * 1024 and int(host.branches["item_count"].max()) == 600
+    assert nc.table_of(case.sbs, table) == nc.written_table(case)
+    _same_table(loader.branches(ds).read(), host, "alone")
+    _check_results(case, results, out_items, out_begin)
+    _check_routes(case, routes)
+    assert np.bincount(routes["route"], minlength=5).min() >= 2
 
 
 def test_no_tasks_and_no_states(loader, decided):

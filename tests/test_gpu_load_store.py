@@ -86,6 +86,28 @@ def test_task_case_equals_the_host_restatement(loader):
     assert loader.last_ndc[0].read().image_bytes() == table0
 
 
+@pytest.mark.parametrize("n_states,n_tasks", sc.nc.LARGE_CASES)
+def test_task_case_past_one_element_per_scan_thread(loader, n_states, n_tasks):
+    """The checksum rows with more than 1024 states and tasks (ndc_load_cases.LARGE_CASES: the branch table and the
+    tasks' rows they read come out of scans whose threads hold several elements each): the rows equal the Python
+    expectation (oracle/checksum_py + zlib over the values written) and the host restatement's.
+
+    (1300, 2500): BACKFILLED / NOT_LOADED / NO_ROUTE / NEW_BRANCH / NOT_RESUMED 160 / 11 / 1735 / 73 / 521.
+    (1025, 1025): 71 / 7 / 730 / 18 / 199."""
+    c = sc.routed_case(n_states, n_tasks)
+    assert c.sbs.n_wf == n_states > 1024 and c.tasks.shape[0] == n_tasks > 1024
+    ds = loader.upload(c.sbs)
+    loader.plan(ds)
+    results, routes, _out = loader.ndc_prepare(ds, c.tasks, sc.nc.task_case(n_states, n_tasks).incoming)
+    got = loader.store_checksums(ds, c.tasks, c.last_events)
+    _same(got, c.want, "task_case")
+    assert got.tobytes() == store_checksums_host(c.sbs, c.tasks, c.last_events, results, routes).tobytes()
+    outcomes = np.bincount(got["outcome"], minlength=len(O))
+    assert set(np.nonzero(outcomes)[0]) == {int(O.BACKFILLED), int(O.NOT_LOADED), int(O.NO_ROUTE), int(O.NEW_BRANCH), int(O.NOT_RESUMED)}
+    assert outcomes[O.BACKFILLED] >= 50 and outcomes[O.NOT_RESUMED] >= 150 and outcomes[O.NEW_BRANCH] >= 10
+    assert (got["outcome"][n_tasks // 2:] == O.BACKFILLED).sum() >= 10     # behind the scan's first threads too
+
+
 def test_empty_state_batch(loader):
     empty = persisted.build_blob_set([])
     ds = loader.upload(empty)

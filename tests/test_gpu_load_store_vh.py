@@ -131,6 +131,32 @@ def test_task_case_equals_the_host_restatement_and_reads_only(loader):
     assert loader.last_ndc[0].read().image_bytes() == table0 and loader.read().image_bytes() == image0
 
 
+@pytest.mark.parametrize("n_states,n_tasks", nc.LARGE_CASES)
+def test_task_case_past_one_element_per_scan_thread(loader, n_states, n_tasks):
+    """More than 1024 tasks (ndc_load_cases.LARGE_CASES): the scans that turn the tasks' lengths into blob offsets and
+    their marks into the generated count give each thread several elements, a clipped last chunk and idle threads
+    behind it.  Rows, offsets and bytes equal the host restatement's and the expected blobs; blob_off is the
+    exclusive prefix of len; n_generated counts the generated tasks; the guard bytes stay intact.
+
+    (1300, 2500): 160 blobs, 57,869 bytes, 91 of them behind task 1024.  (1025, 1025): 71 blobs, 26,166 bytes."""
+    c = sc.routed_case(n_states, n_tasks)
+    assert c.sbs.n_wf == n_states > 1024 and c.tasks.shape[0] == n_tasks > 1024
+    ds = loader.upload(c.sbs)
+    loader.plan(ds)
+    results, routes, _out = loader.ndc_prepare(ds, c.tasks, nc.task_case(n_states, n_tasks).incoming)
+    plan = loader.store_version_histories_plan(ds, c.tasks, c.last_events)
+    data, tail, intact, _buf = _guarded_run(loader, plan)
+    rows, off = _read(plan)
+    host = store_version_histories_host(c.sbs, c.tasks, c.last_events, results, routes)
+    _same((rows, off, data), host, "task_case")
+    assert intact and (tail == 0).all()
+    vb.assert_blobs(rows, off, data, vb.routed_expected(c, n_states, n_tasks), "task_case")
+    assert (off == np.concatenate([[0], np.cumsum(rows["len"].astype(np.uint64))]).astype(np.uint64)).all()
+    generated = rows["len"] > 0
+    assert int(plan.sizes.n_generated) == int(generated.sum()) >= 50 and int(plan.sizes.n_bytes) == int(off[-1]) > 20_000
+    assert (generated == np.isin(c.want["outcome"], vb.GENERATED)).all() and generated[n_tasks // 2:].sum() >= 10
+
+
 @pytest.mark.parametrize("name", ["seams", "large"])
 def test_seams_and_one_large_state(loader, name):
     (sbs, tasks, last, results, routes), want = vb.seam_case() if name == "seams" else vb.large_case()
@@ -236,6 +262,26 @@ def test_end_to_end_through_the_wave_tail(engine, loader):
     in_tail = pos >= lay.wave_begin
     assert (applied & in_tail).sum() >= 5 and (applied & ~in_tail).sum() >= 5 and (applied & two & in_tail).any()
     assert (applied & two).sum() >= 5 and (applied & ~two).sum() >= 5 and (rows["outcome"] == O.BACKFILLED).sum() >= 3
+
+
+def test_end_to_end_past_1024_states_and_tasks(engine, loader):
+    """store_cases.replayed_case_large through upload, plan, decide and route, place, replay and generate: 1400 states
+    and 1366 tasks (683 two-branch states), 1138 APPLIED and 228 BACKFILLED, 293 and 49 of them at task index 1024
+    or above -- behind the first element of every scan thread.  The checksum rows and the blobs equal the values
+    expected from the values written and the oracle's rows."""
+    rc = sc.replayed_case_large()
+    assert rc.sbs.n_wf > 1024 and rc.tasks.shape[0] > 1024
+    plan, sums, want, blobs, lay, _pos, *_ = _end_to_end(engine, loader, rc, interleave)
+    assert lay.stride == 64 and lay.n_wf > 1024
+    rows, _off, _data = _check_end_to_end(loader, rc, plan, sums, want, blobs, "1400 states")
+    for f in abi.STORE_ROW.names:
+        bad = np.nonzero(sums[f] != want[f])[0]
+        assert bad.size == 0, f"checksum rows, {f}: {bad.size} tasks differ, first {bad[:5]}"
+    assert int(plan.sizes.n_generated) == int((rows["len"] > 0).sum()) == rows.shape[0]
+    past = rows["outcome"][1024:]
+    assert (past == O.APPLIED).sum() >= 100 and (past == O.BACKFILLED).sum() >= 20
+    applied, two = rows["outcome"] == O.APPLIED, rc.two_branch[rc.tasks["wf"]]
+    assert (applied & two)[1024:].sum() >= 20 and (applied & ~two)[1024:].sum() >= 20
 
 
 def test_garbage_counts_stay_within_the_descriptor_and_the_lanes_own_bytes(engine, loader):

@@ -262,7 +262,8 @@ def test_live_id_sidecar_matches_rows_every_path(eng):
     """The live-ID sidecar (crr_outputs.live_ids, ABI v6) holds, for every OK workflow, the IDs of its live rows
     in slots 0..n-1 of each pending map (the checksum's lists) on every kernel path -- tier segments, retry
     pass, wavefront tail / big kernels, canonical global kernel, task emission, a passive-replication step --
-    and crr_checksum reading it equals crr_checksum reading the rows and the replay's own checksums."""
+    and crr_checksum reading it equals crr_checksum reading the rows (for every workflow, the failed ones included:
+    those are read from the rows on both paths) and the replay's own checksums."""
     import ctypes
     import torch
     from cadence_amd.replication import PassiveReplication
@@ -304,6 +305,8 @@ def test_live_id_sidecar_matches_rows_every_path(eng):
         rows_cs = out.cpu().numpy().view(np.uint32)[:db.n_wf]
         assert (with_side[ok] == res.exec["checksum"][ok]).all(), name
         assert (rows_cs[ok] == res.exec["checksum"][ok]).all(), name
+        # every workflow, the failed ones too: they have counts but no sidecar slots, and are read from the rows
+        assert (with_side == rows_cs).all(), name
         return n_ids
 
     total = 0

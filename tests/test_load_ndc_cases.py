@@ -5,6 +5,7 @@ prepareVersionHistory under the oracle and every route of prepareMutableState un
 reference's own two answers (conflict_resolver_test.go:171-187, :189-260).
 """
 import numpy as np
+import pytest
 
 from cadence_amd import abi
 from cadence_amd.abi import Status
@@ -40,6 +41,38 @@ def test_the_tasks_cover_every_route():
     # rebuilds from a stored branch and from the new one
     rb = routes[routes["route"] == abi.ROUTE_REBUILD]
     assert set(int(x) for x in rb["branch_is_local"]) == {0, 1}
+
+
+# per size: (tasks per route NONE / APPLY_CURRENT / NON_CURRENT / REBUILD / BAD_REQUEST, branches, tasks not decided,
+# items of new-branch room)
+LARGE_COUNTS = {(1300, 2500): ([1346, 521, 233, 388, 12], 3392, 11, 12323),
+                (1025, 1025): ([570, 199, 89, 165, 2], 2699, 7, 4779)}
+
+
+@pytest.mark.parametrize("n_states,n_tasks", nc.LARGE_CASES)
+def test_the_large_cases_cover_every_decision_and_route(n_states, n_tasks):
+    """The sizes the GPU tests use past 1024 states and tasks are not degenerate: every decision, every route, both
+    kinds of rebuild, and the states are what the tasks were built from."""
+    case = nc.task_case(n_states, n_tasks)
+    assert case.sbs.n_wf == n_states > 1024 and len(case.tasks) == n_tasks > 1024
+    # the chunk of a 1024-thread scan: more than one element and idle threads behind the last one, over the states
+    # and over the tasks; the tasks' last chunk is not full
+    for n in (n_states, n_tasks):
+        per = -(-n // 1024)
+        assert per >= 2 and -(-n // per) < 1024
+    assert n_tasks % -(-n_tasks // 1024) != 0
+    _idx, _batch, res, _out = nc.oracle_decisions(case)
+    assert {0, int(Status.NDC_NO_LCA), int(Status.NDC_RETRY_TASK)} <= set(int(s) for s in res["status"])
+    assert set(int(a) for a, s in zip(res["action"], res["status"]) if s == 0) == {abi.NDC_APPEND, abi.NDC_NEW_BRANCH, abi.NDC_DUPLICATE}
+    results, routes, _items = nc.expected_routes(case)
+    host = load_branches_host(case.sbs)
+    room = sum(max(len(b) for b in t.local) for t in case.ndc_tasks if t is not None)
+    not_decided = sum(t is None for t in case.ndc_tasks)
+    assert (np.bincount(routes["route"], minlength=5).tolist(), host.branches.shape[0], not_decided, room) == LARGE_COUNTS[(n_states, n_tasks)]
+    rb = routes[routes["route"] == abi.ROUTE_REBUILD]
+    assert set(int(x) for x in rb["branch_is_local"]) == {0, 1}
+    assert nc.table_of(case.sbs, host) == nc.written_table(case)
+    assert tuple(routes[case.known["rebuild"]]) == (abi.ROUTE_REBUILD, 0, 2, 0, 1, 12)
 
 
 def test_an_empty_current_branch_is_vh_empty():

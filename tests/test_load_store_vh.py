@@ -175,6 +175,48 @@ def test_replayed_states_applied_and_backfilled():
     assert (applied & two).sum() >= 15 and (applied & ~two).sum() >= 15 and (rows["outcome"] == O.BACKFILLED).sum() >= 5
 
 
+# per size: (BACKFILLED / NOT_LOADED / NO_ROUTE / NEW_BRANCH / NOT_RESUMED tasks, bytes, blobs behind the middle task)
+LARGE_COUNTS = {(1300, 2500): ([160, 11, 1735, 73, 521], 57869, 80), (1025, 1025): ([71, 7, 730, 18, 199], 26166, 29)}
+
+
+@pytest.mark.parametrize("n_states,n_tasks", nc.LARGE_CASES)
+def test_the_large_task_cases_cover_every_outcome(n_states, n_tasks):
+    """The sizes the GPU tests use past 1024 states and tasks: the host restatement's checksum rows and blobs equal the
+    expected ones, the five outcomes a call without replayed states can give are all there, and generated blobs lie in
+    both halves of the tasks."""
+    c = sc.routed_case(n_states, n_tasks)
+    assert c.sbs.n_wf == n_states and c.tasks.shape[0] == n_tasks
+    sums = store_checksums_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    assert sums.tobytes() == c.want.tobytes()
+    rows, off, data = store_version_histories_host(c.sbs, c.tasks, c.last_events, c.results, c.routes)
+    _same_decision(rows, c.want, "task_case")
+    vb.assert_blobs(rows, off, data, vb.routed_expected(c, n_states, n_tasks), "task_case")
+    kinds = [O.BACKFILLED, O.NOT_LOADED, O.NO_ROUTE, O.NEW_BRANCH, O.NOT_RESUMED]
+    assert set(int(x) for x in rows["outcome"]) == set(int(k) for k in kinds)
+    behind = int((rows["len"][n_tasks // 2:] > 0).sum())
+    assert ([int((rows["outcome"] == k).sum()) for k in kinds], int(off[-1]), behind) == LARGE_COUNTS[(n_states, n_tasks)]
+    assert behind >= 10
+
+
+def test_the_large_replayed_case_has_both_generated_outcomes_past_task_1024():
+    """store_cases.replayed_case_large: 1400 states, 1366 tasks, 1138 APPLIED and 228 BACKFILLED; at task index 1024 or
+    above 293 and 49, the applied ones on 126 two-branch and 167 single-branch states."""
+    rc = sc.replayed_case_large()
+    res, routes = sc.decided(rc)
+    resumed = persisted.apply_mask(routes, rc.tasks, rc.sbs.n_wf)
+    after = rc.one_r.to_loaded(rc.one_b, mask=resumed)
+    want = sc.expected_replayed(rc, routes, res, resumed, after)
+    sums = store_checksums_host(rc.sbs, rc.tasks, rc.last_events, res, routes, after)
+    assert sums.tobytes() == want.tobytes()
+    rows, off, data = store_version_histories_host(rc.sbs, rc.tasks, rc.last_events, res, routes, after)
+    vb.assert_blobs(rows, off, data, vb.replayed_expected(rc, want, after), "large replayed case")
+    applied, two = want["outcome"] == O.APPLIED, rc.two_branch[rc.tasks["wf"]]
+    counts = (rc.sbs.n_wf, rc.tasks.shape[0], int(applied.sum()), int((want["outcome"] == O.BACKFILLED).sum()),
+              int(applied[1024:].sum()), int((want["outcome"][1024:] == O.BACKFILLED).sum()),
+              int((applied & two)[1024:].sum()), int((applied & ~two)[1024:].sum()))
+    assert counts == (1400, 1366, 1138, 228, 293, 49, 126, 167)
+
+
 def test_round_trip_applied_blobs_load_and_verify():
     """The states after their task as the store would hold them (the whole histories' replay persisted), their
     field 122 replaced by the generated blob and the generated checksum stored: they load to the expected table and

@@ -120,8 +120,8 @@ def hand_modes(c: sc.StoreCase, want: np.ndarray):
 
 
 # ---- store_cases.routed_case -------------------------------------------------------------------------------------
-def routed_histories(c: sc.StoreCase, k: int):
-    case = nc.task_case()
+def routed_histories(c: sc.StoreCase, k: int, n_states: int = 130, n_tasks: int = 400, seed: int = 3, big: bool = True):
+    case = nc.task_case(n_states, n_tasks, seed, big)
     w, b = int(c.tasks[k]["wf"]), int(c.results[k]["branch_index"])
     cur, local = case.locals_[w]
     hs = sc._written(w, local)
@@ -131,8 +131,10 @@ def routed_histories(c: sc.StoreCase, k: int):
     return cur, hs
 
 
-def routed_expected(c: sc.StoreCase) -> List[Optional[bytes]]:
-    return [expected_blob(*routed_histories(c, k)) if int(c.want[k]["outcome"]) in GENERATED else None
+def routed_expected(c: sc.StoreCase, n_states: int = 130, n_tasks: int = 400, seed: int = 3, big: bool = True
+                    ) -> List[Optional[bytes]]:
+    """The blobs expected for ``c = store_cases.routed_case(...)`` of the same arguments."""
+    return [expected_blob(*routed_histories(c, k, n_states, n_tasks, seed, big)) if int(c.want[k]["outcome"]) in GENERATED else None
             for k in range(c.want.shape[0])]
 
 
