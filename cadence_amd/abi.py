@@ -369,6 +369,27 @@ class CVhBlobSizes(ctypes.Structure):
                 ("n_bytes", ctypes.c_uint64), ("work_needed", ctypes.c_uint64)]
 
 
+# ---- the pending-entry mutation to store for routed tasks (include/cadence_load_mutation.h) ----------------
+MUTATION_MAPS = ["act", "timer", "child", "rc", "sig"]     # crr_mutation_row.map / crr_mutation_out order
+MUTATION_MAP = np.dtype([("upsert_begin", "<u4"), ("n_upsert", "<u4"), ("delete_begin", "<u4"), ("n_delete", "<u4")])
+MUTATION_ROW = np.dtype([("outcome", "<i4"), ("status", "<i4"), ("flags", "<u4"), ("exec_index", "<u4"),
+                         ("map", MUTATION_MAP, (len(MUTATION_MAPS),))])
+MUTATION_RESET_POINTS_CHANGED = 1             # CRR_MUTATION_RESET_POINTS_CHANGED
+MUTATION_NO_EXEC = 0xFFFFFFFF                 # crr_mutation_row.exec_index of a task without an exec row
+
+
+class CMutationSizes(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_int32), ("n_tasks", ctypes.c_uint32), ("n_exec", ctypes.c_uint64),
+                ("n_upsert", ctypes.c_uint64 * 5), ("n_delete", ctypes.c_uint64 * 5),
+                ("work_needed", ctypes.c_uint64), ("run_work_needed", ctypes.c_uint64)]
+
+
+class CMutationOut(ctypes.Structure):
+    _fields_ = [("exec", ctypes.c_void_p), ("exec_capacity", ctypes.c_uint64),
+                ("upsert", ctypes.c_void_p * 5), ("upsert_capacity", ctypes.c_uint64 * 5),
+                ("deleted", ctypes.c_void_p * 5), ("delete_capacity", ctypes.c_uint64 * 5)]
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -438,10 +459,12 @@ def check_layout(lib):
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {got} vs numpy {dt.itemsize}")
     for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize),
                  (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize),
-                 (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize), (30, VH_BLOB_ROW.itemsize)):
+                 (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize), (30, VH_BLOB_ROW.itemsize),
+                 (33, MUTATION_ROW.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
     for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage),
-                  (24, CLoadBranches), (25, CLoadNdcSizes), (31, CVhBlobSizes)):
+                  (24, CLoadBranches), (25, CLoadNdcSizes), (31, CVhBlobSizes), (34, CMutationSizes),
+                  (35, CMutationOut)):
         if lib.crr_sizeof(i) != ctypes.sizeof(st):
             raise RuntimeError(f"ABI layout mismatch for {st.__name__}: C {lib.crr_sizeof(i)} vs ctypes {ctypes.sizeof(st)}")

@@ -7,6 +7,7 @@
 
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
+#include "cadence_load_mutation.h"
 #include "cadence_load_store.h"
 #include "cadence_load_store_vh.h"
 #include "cadence_load_verify.h"
@@ -272,6 +273,9 @@ size_t crr_sizeof(int which) {
     case 28: return sizeof(crr_last_event);
     case 30: return sizeof(crr_vh_blob_row);
     case 31: return sizeof(crr_vh_blob_sizes);
+    case 33: return sizeof(crr_mutation_row);
+    case 34: return sizeof(crr_mutation_sizes);
+    case 35: return sizeof(crr_mutation_out);
     default: return 0;
   }
 }

@@ -19,6 +19,9 @@
 //   store_task   per task      (on request, cadence_load_store.h) the checksum to store once the routed task is
 //                              committed: the payload written once behind a state view (payload_head ...), from the
 //                              rows a resumed replay left or from the loaded image with the task's last event
+//   mutation_count_task / mutation_emit_task   per task  (on request, cadence_load_mutation.h) the pending entries
+//                              to upsert and the keys to delete for the same decision: one merge walk per pending
+//                              map (mutation_walk) over the loaded image before and the state view after
 //
 // Wire format: thrift binary (big-endian; field header = type byte + i16 id, 0 ends a struct), field IDs of
 // .gen/go/sqlblobs/sqlblobs.go restated below (tests/golden/sqlblobs_fields.json pins them); a field whose
@@ -34,6 +37,7 @@
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
 #include "cadence_load_store.h"
+#include "cadence_load_mutation.h"
 #include "cadence_load_store_vh.h"
 #include "cadence_load_verify.h"
 
@@ -1250,10 +1254,16 @@ struct StateView {
   const crr_vh_item* vh;                           // item 0 of the current branch
   uint32_t n_act, n_timer, n_child, n_rc, n_sig, n_vh;
   uint64_t stride;                                 // rows between two live rows
+  // what only the mutation reads (cadence_load_mutation.h): the reset points, and where the exec row lies in its
+  // table (the device position, or the workflow for a dense image)
+  const uint8_t* rp;
+  uint32_t n_rp;
+  uint64_t exec_slot;
 
   CRR_HD uint32_t count(int t) const { return t == 0 ? n_act : t == 1 ? n_timer : t == 2 ? n_child : t == 3 ? n_rc : n_sig; }
+  CRR_HD const uint8_t* rows_of(int t) const { return t == 0 ? act : t == 1 ? timer : t == 2 ? child : t == 3 ? rc : sig; }
   CRR_HD int64_t id(int t, uint32_t j) const {     // the ID a row's first field
-    const uint8_t* p = t == 0 ? act : t == 1 ? timer : t == 2 ? child : t == 3 ? rc : sig;
+    const uint8_t* p = rows_of(t);
     int64_t v;
     memcpy(&v, p + (uint64_t)j * stride * kRowBytes[t], sizeof v);
     return v;
@@ -1276,6 +1286,7 @@ CRR_HD StateView scratch_view(const Ctx& c, uint32_t w) {
   S.act = row0(0), S.timer = row0(1), S.child = row0(2), S.rc = row0(3), S.sig = row0(4);
   S.vh = reinterpret_cast<const crr_vh_item*>(row0(5));
   S.n_act = n(0), S.n_timer = n(1), S.n_child = n(2), S.n_rc = n(3), S.n_sig = n(4), S.n_vh = n(5);
+  S.rp = row0(6), S.n_rp = n(6), S.exec_slot = w;
   S.stride = 1;
   return S;
 }
@@ -1368,6 +1379,7 @@ struct ReplayAfter {
     S.n_act = bounded_count(S.R.n_activity, D.act_cap, out.act), S.n_timer = bounded_count(S.R.n_timer, D.timer_cap, out.timer);
     S.n_child = bounded_count(S.R.n_child, D.child_cap, out.child), S.n_rc = bounded_count(S.R.n_rc, D.rc_cap, out.rc);
     S.n_sig = bounded_count(S.R.n_signal, D.sig_cap, out.sig), S.n_vh = bounded_count(S.R.n_vh_items, D.vh_cap, out.vh);
+    S.rp = row0(out.rp, D.rp_base, 6), S.n_rp = bounded_count(S.R.n_reset_points, D.rp_cap, out.rp), S.exec_slot = p;
     return true;
   }
 };
@@ -1390,6 +1402,7 @@ struct ImageAfter {
     S.vh = reinterpret_cast<const crr_vh_item*>(row0(5));
     S.n_act = n(0, S.R.n_activity), S.n_timer = n(1, S.R.n_timer), S.n_child = n(2, S.R.n_child), S.n_rc = n(3, S.R.n_rc);
     S.n_sig = n(4, S.R.n_signal), S.n_vh = n(5, S.R.n_vh_items);
+    S.rp = row0(6), S.n_rp = n(6, S.R.n_reset_points), S.exec_slot = w;
     return true;
   }
 };
@@ -1694,6 +1707,201 @@ CRR_HD void vh_emit_chunk(const Ctx& c, const StoreIn& a, const After& after, co
     if (b < 8) lo |= (uint64_t)v << (8 * b);
     else hi |= (uint64_t)v << (8 * (b - 8));
   }
+}
+
+// ---- per task: the pending-entry mutation to store (cadence_load_mutation.h) ----------------------------------
+// What CloseTransactionAsMutation writes beside ExecutionInfo (mutable_state_builder.go:4002-4011): per pending map
+// the rows to upsert and the keys to delete, as the difference between the loader's dense image (before) and the
+// state the resumed replay left (after), both behind the state view store_task reads.  The walk is written once
+// and takes a visitor: the count pass counts, the emit pass writes the deleted keys and the directory.
+static_assert(sizeof(crr_activity_row) == 112 && sizeof(crr_timer_row) == 40 && sizeof(crr_child_row) == 48 &&
+                  sizeof(crr_initiated_row) == 32 && sizeof(crr_reset_point_row) == 16 && sizeof(crr_exec_row) == 208,
+              "row images are compared and gathered as 8-byte words");
+static_assert(__builtin_offsetof(crr_activity_row, last_hb_timeout_vis_s) == 56 && __builtin_offsetof(crr_activity_row, flags) == 96 &&
+                  __builtin_offsetof(crr_child_row, flags) == 40 && __builtin_offsetof(crr_timer_row, key) == 28,
+              "the masks of mut_mask and the timer's key");
+
+constexpr uint64_t kMutNoSlot = ~0ull;   // a directory entry the emit pass did not write
+
+CRR_HD uint64_t mut_word(const uint8_t* row, uint32_t k) {
+  uint64_t v;
+  memcpy(&v, row + 8u * k, sizeof v);
+  return v;
+}
+// the persisted bits of word k of map t's row image: not the activity's last_hb_timeout_vis_s (word 7) and MAPPED
+// flag (the low half of word 12), nor the child row's reserved word (the high half of word 5)
+CRR_HD uint64_t mut_mask(int t, uint32_t k) {
+  if (t == 0) return k == 7 ? 0ull : k == 12 ? ~(uint64_t)CRR_ROW_MAPPED : ~0ull;
+  if (t == 2) return k == 5 ? 0xFFFFFFFFull : ~0ull;
+  return ~0ull;
+}
+template <int T>
+CRR_HD bool mut_same(const uint8_t* a, const uint8_t* b) {
+  uint64_t diff = 0;
+  for (uint32_t k = 0; k < kRowBytes[T] / 8; ++k) diff |= (mut_word(a, k) ^ mut_word(b, k)) & mut_mask(T, k);
+  return diff == 0;
+}
+CRR_HD uint32_t mut_timer_key(const uint8_t* row) {
+  uint32_t v;
+  memcpy(&v, row + 28, sizeof v);
+  return v;
+}
+
+// map T of one task: B the rows before, A the rows after, both ascending by their first field.  vis.upsert(row
+// after) in slot order, vis.remove(key) in the order of the rows before.
+template <int T, class Vis>
+CRR_HD void mutation_walk(const StateView& B, const StateView& A, Vis& vis) {
+  const uint8_t *pb = B.rows_of(T), *pa = A.rows_of(T);
+  const uint64_t sb = B.stride * kRowBytes[T], sa = A.stride * kRowBytes[T];
+  const uint32_t nb = B.count(T), na = A.count(T);
+  auto gone = [&](const uint8_t* rb) {
+    if (T != 1) return vis.remove((int64_t)mut_word(rb, 0));
+    // a timer is the store's row of its TimerID: started again under it, the row is replaced, not deleted
+    const uint32_t key = mut_timer_key(rb);
+    for (uint32_t j = 0; j < na; ++j)
+      if (mut_timer_key(pa + j * sa) == key) return;
+    vis.remove((int64_t)key);
+  };
+  uint32_t i = 0, j = 0;
+  while (i < nb || j < na) {
+    const uint8_t *rb = pb + i * sb, *ra = pa + j * sa;
+    if (j >= na) { gone(rb); ++i; continue; }
+    if (i >= nb) { vis.upsert(ra); ++j; continue; }
+    const int64_t ib = (int64_t)mut_word(rb, 0), ia = (int64_t)mut_word(ra, 0);
+    if (ib < ia) { gone(rb); ++i; continue; }
+    if (ia < ib) { vis.upsert(ra); ++j; continue; }
+    if (T == 1 && mut_timer_key(rb) != mut_timer_key(ra)) {   // one started_id under two TimerIDs: two store rows
+      gone(rb);
+      vis.upsert(ra);
+    } else if (!mut_same<T>(rb, ra)) {
+      vis.upsert(ra);
+    }
+    ++i, ++j;
+  }
+}
+
+CRR_HD bool mut_reset_points_differ(const StateView& B, const StateView& A) {
+  if (B.n_rp != A.n_rp) return true;
+  uint64_t diff = 0;
+  for (uint32_t j = 0; j < A.n_rp; ++j) {
+    const uint8_t *rb = B.rp + (uint64_t)j * B.stride * kRowBytes[6], *ra = A.rp + (uint64_t)j * A.stride * kRowBytes[6];
+    diff |= (mut_word(rb, 0) ^ mut_word(ra, 0)) | (mut_word(rb, 1) ^ mut_word(ra, 1));
+  }
+  return diff != 0;
+}
+
+// the decision of store_task, its branch-table check included: true when the task has a pending-entry mutation
+template <class After>
+CRR_HD bool mutation_decide(const Ctx& c, const StoreIn& a, const After& after, uint32_t idx, StoreDecision& D,
+                            int32_t& outcome, int32_t& status) {
+  store_decide(c, a, after, idx, D);
+  outcome = D.outcome, status = D.status;
+  if (D.generated()) {
+    for (int64_t h = 0; h < D.nb; ++h) {
+      StoreBranch B;
+      if (!store_branch(a, D, h, B)) {
+        outcome = CRR_STORE_NOT_LOADED;
+        break;
+      }
+    }
+  }
+  return outcome == CRR_STORE_APPLIED;
+}
+
+struct MutCount {
+  uint32_t up, del;
+  CRR_HD void upsert(const uint8_t*) { ++up; }
+  CRR_HD void remove(int64_t) { ++del; }
+};
+
+// task idx's row with its counts (the begins zero: the offsets pass fills them); exec_index 0 marks an exec row
+template <class After>
+CRR_HD void mutation_count_task(const Ctx& c, const StoreIn& a, const After& after, uint32_t idx, crr_mutation_row& o) {
+  memset(&o, 0, sizeof o);
+  o.exec_index = 0xFFFFFFFFu;
+  StoreDecision D;
+  if (!mutation_decide(c, a, after, idx, D, o.outcome, o.status)) return;
+  const StateView B = scratch_view(c, D.w);
+  o.exec_index = 0;
+  if (mut_reset_points_differ(B, D.S)) o.flags |= CRR_MUTATION_RESET_POINTS_CHANGED;
+  MutCount k0 = {0, 0}, k1 = {0, 0}, k2 = {0, 0}, k3 = {0, 0}, k4 = {0, 0};
+  mutation_walk<0>(B, D.S, k0);
+  mutation_walk<1>(B, D.S, k1);
+  mutation_walk<2>(B, D.S, k2);
+  mutation_walk<3>(B, D.S, k3);
+  mutation_walk<4>(B, D.S, k4);
+  o.map[0].n_upsert = k0.up, o.map[0].n_delete = k0.del;
+  o.map[1].n_upsert = k1.up, o.map[1].n_delete = k1.del;
+  o.map[2].n_upsert = k2.up, o.map[2].n_delete = k2.del;
+  o.map[3].n_upsert = k3.up, o.map[3].n_delete = k3.del;
+  o.map[4].n_upsert = k4.up, o.map[4].n_delete = k4.del;
+}
+
+// The run call's directory and key buffers.  dir_exec[k]: the slot of exec row k in the after-state's exec table;
+// dir[t][k]: the row index, in the after-state's table t, of upserted row k.  Both are preset to kMutNoSlot.
+struct MutDst {
+  uint64_t* dir_exec;
+  uint64_t* dir[CRR_MUTATION_MAPS];
+  int64_t* keys[CRR_MUTATION_MAPS];
+  const uint8_t* base[CRR_MUTATION_MAPS];   // row 0 of the after-state's tables
+  uint64_t n_exec, n_upsert[CRR_MUTATION_MAPS], n_delete[CRR_MUTATION_MAPS];   // the plan's totals
+};
+
+struct MutEmit {
+  uint64_t* dir;
+  int64_t* keys;
+  const uint8_t* base;
+  uint32_t row_bytes, up, del, n_up, n_del;
+  CRR_HD void upsert(const uint8_t* ra) {
+    if (up < n_up) dir[up] = (uint64_t)(ra - base) / row_bytes;
+    ++up;
+  }
+  CRR_HD void remove(int64_t key) {
+    if (del < n_del) keys[del] = key;
+    ++del;
+  }
+};
+
+// the walk again for planned row `o`: nothing is written outside the ranges the plan gave the task, and a range
+// that does not lie within the plan's totals is not written at all; keys the walk no longer finds are zeros
+template <int T>
+CRR_HD void mutation_emit_map(const StateView& B, const StateView& A, const crr_mutation_map& m, const MutDst& d, bool walk) {
+  const bool up_ok = (uint64_t)m.upsert_begin + m.n_upsert <= d.n_upsert[T];
+  const bool del_ok = (uint64_t)m.delete_begin + m.n_delete <= d.n_delete[T];
+  MutEmit e = {d.dir[T] + m.upsert_begin, d.keys[T] + m.delete_begin, d.base[T], kRowBytes[T], 0, 0,
+               up_ok ? m.n_upsert : 0u, del_ok ? m.n_delete : 0u};
+  if (walk) mutation_walk<T>(B, A, e);
+  for (uint32_t k = e.del; k < e.n_del; ++k) e.keys[k] = 0;
+}
+
+template <class After>
+CRR_HD void mutation_emit_task(const Ctx& c, const StoreIn& a, const After& after, uint32_t idx, const crr_mutation_row* rows,
+                               const MutDst& d) {
+  const crr_mutation_row o = rows[idx];
+  StoreDecision D;
+  int32_t outcome, status;
+  const bool walk = mutation_decide(c, a, after, idx, D, outcome, status);
+  if (!walk) {   // no longer a mutation: its keys are zeros, its directory entries stay unwritten (the views are not read)
+    mutation_emit_map<0>(D.S, D.S, o.map[0], d, false);
+    mutation_emit_map<1>(D.S, D.S, o.map[1], d, false);
+    mutation_emit_map<2>(D.S, D.S, o.map[2], d, false);
+    mutation_emit_map<3>(D.S, D.S, o.map[3], d, false);
+    mutation_emit_map<4>(D.S, D.S, o.map[4], d, false);
+    return;
+  }
+  const StateView B = scratch_view(c, D.w);
+  if (o.exec_index < d.n_exec) d.dir_exec[o.exec_index] = D.S.exec_slot;
+  mutation_emit_map<0>(B, D.S, o.map[0], d, walk);
+  mutation_emit_map<1>(B, D.S, o.map[1], d, walk);
+  mutation_emit_map<2>(B, D.S, o.map[2], d, walk);
+  mutation_emit_map<3>(B, D.S, o.map[3], d, walk);
+  mutation_emit_map<4>(B, D.S, o.map[4], d, walk);
+}
+
+// word g of a dense output of `words`-word rows, gathered through its directory from `table`
+CRR_HD uint64_t mutation_gather_word(const uint64_t* table, const uint64_t* dir, uint32_t words, uint64_t g) {
+  const uint64_t src = dir[g / words];
+  return src == kMutNoSlot ? 0ull : table[src * words + g % words];
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

@@ -21,6 +21,11 @@
 //   load_store_vh_size_kernel / load_store_vh_emit_kernel   the VersionHistories blob to store for the same tasks
 //                       (cadence_load_store_vh.h): one lane per task sizes it, load_ndc_scan_kernel gives the offsets,
 //                       then one lane per 16 bytes of the output writes them with one dwordx4 store
+//   load_mutation_count_kernel / load_mutation_offsets_kernel / load_mutation_emit_kernel / load_mutation_gather_kernel
+//                       the pending-entry mutation to store for the same tasks (cadence_load_mutation.h): one lane per
+//                       task classifies its entries by a merge walk and counts, the block sums are scanned by
+//                       load_ndc_scan_kernel and one pass turns the counts into offsets; then one lane per task writes
+//                       the deleted keys and a directory, and one lane per 8-byte word gathers the rows through it
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -284,6 +289,101 @@ __global__ void __launch_bounds__(kBlock) load_store_vh_emit_kernel(Ctx c, Store
   uint64_t lo, hi;
   vh_emit_chunk(c, a, after, blob_off, n_bytes, i, lo, hi);
   out[i] = make_ulonglong2(lo, hi);
+}
+
+// ---- cadence_load_mutation.h: the pending-entry mutation to store for every routed task ------------------------
+// The columns that are counted, scanned and turned into offsets: the exec rows, then per map its upserted rows and
+// its deleted keys.
+constexpr int kMutCols = 1 + 2 * CRR_MUTATION_MAPS;
+
+__device__ inline uint32_t mut_col(const crr_mutation_row& o, int col) {
+  if (col == 0) return o.exec_index != 0xFFFFFFFFu ? 1u : 0u;
+  const crr_mutation_map& m = o.map[(col - 1) / 2];
+  return (col & 1) ? m.n_upsert : m.n_delete;
+}
+
+// one lane per task, load_store_kernel's launch without the CRC: the decision, then one merge walk per pending map
+// over the rows before (the loader's dense image) and after (the replay's slots); the row with its counts, and the
+// block's column sums (LDS atomics: most lanes add to two or three columns) for the offsets
+__global__ void __launch_bounds__(kBlock) load_mutation_count_kernel(Ctx c, StoreIn a, ReplayAfter after, crr_mutation_row* rows,
+                                                                     int64_t* block_sums, uint32_t n_blocks) {
+  __shared__ uint32_t sums[kMutCols];
+  if (threadIdx.x < kMutCols) sums[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < a.n_tasks) {
+    crr_mutation_row o;
+    mutation_count_task(c, a, after, i, o);
+    rows[i] = o;
+#pragma unroll
+    for (int col = 0; col < kMutCols; ++col) {
+      const uint32_t v = mut_col(o, col);
+      if (v) atomicAdd(&sums[col], v);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kMutCols) block_sums[(uint64_t)threadIdx.x * ((uint64_t)n_blocks + 1) + blockIdx.x] = sums[threadIdx.x];
+}
+
+__device__ inline uint32_t wave_inclusive_scan(uint32_t v) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t o = __shfl_up(v, d, 64);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+
+// one pass over the packed count rows: block_base is the scanned block sums ([kMutCols][n_blocks + 1]); within the
+// block each column is a wavefront scan, the first wavefront's total handed over in LDS.  Every lane of the block
+// takes part in the scans, a lane past the last task with zeros.
+__global__ void __launch_bounds__(kBlock) load_mutation_offsets_kernel(crr_mutation_row* rows, uint32_t n_tasks,
+                                                                       const int64_t* block_base, uint32_t n_blocks) {
+  static_assert(kBlock == 128, "two wavefronts of 64");
+  __shared__ uint32_t first_wave[kMutCols];
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool have = i < n_tasks;
+  crr_mutation_row o;
+  if (have) o = rows[i];
+  uint32_t excl[kMutCols];
+#pragma unroll
+  for (int col = 0; col < kMutCols; ++col) {
+    const uint32_t v = have ? mut_col(o, col) : 0u;
+    const uint32_t incl = wave_inclusive_scan(v);
+    if (threadIdx.x == 63) first_wave[col] = incl;
+    excl[col] = incl - v;
+  }
+  __syncthreads();
+  if (!have) return;
+#pragma unroll
+  for (int col = 0; col < kMutCols; ++col) {
+    excl[col] += (uint32_t)block_base[(uint64_t)col * ((uint64_t)n_blocks + 1) + blockIdx.x];
+    if (threadIdx.x >= 64) excl[col] += first_wave[col];
+  }
+  if (o.exec_index != 0xFFFFFFFFu) o.exec_index = excl[0];
+#pragma unroll
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+    o.map[t].upsert_begin = excl[1 + 2 * t];
+    o.map[t].delete_begin = excl[2 + 2 * t];
+  }
+  rows[i] = o;
+}
+
+// one lane per task: the walk again, the deleted keys to their planned ranges and the directory to the work buffer
+__global__ void __launch_bounds__(kBlock) load_mutation_emit_kernel(Ctx c, StoreIn a, ReplayAfter after, const crr_mutation_row* rows,
+                                                                    MutDst d) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < a.n_tasks) mutation_emit_task(c, a, after, i, rows, d);
+}
+
+// output-stationary, compact_gather_kernel's reasoning: lane g owns 8-byte word g of a dense output and finds its
+// row through the directory, so a wavefront's stores are one contiguous 512 bytes and no store address depends on
+// anything but the lane's index
+__global__ void __launch_bounds__(kBlock) load_mutation_gather_kernel(const uint64_t* table, const uint64_t* dir, uint32_t words,
+                                                                      uint64_t n_words, uint64_t* out) {
+  const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g < n_words) out[g] = mutation_gather_word(table, dir, words, g);
 }
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
@@ -710,6 +810,147 @@ int crr_load_store_vh_run(const crr_state_batch* in, const void* scratch, size_t
   if (n_chunks == 0) return 0;
   hipLaunchKernelGGL(load_store_vh_emit_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, c, a, after, blob_off,
                      plan_host->n_bytes, n_chunks, reinterpret_cast<ulonglong2*>(out));
+  return (int)hipGetLastError();
+}
+
+// ---- cadence_load_mutation.h ----------------------------------------------------------------------------------
+// the plan's work buffer: the block sums [kMutCols][n_blocks + 1] (scanned in place), then the totals
+struct MutPlanLayout {
+  uint64_t sums, totals, end;
+  uint32_t n_blocks;
+};
+static MutPlanLayout carve_mut_plan(uint32_t n_tasks) {
+  MutPlanLayout L;
+  L.n_blocks = (uint32_t)(((uint64_t)n_tasks + kBlock - 1) / kBlock);
+  uint64_t o = 0;
+  L.sums = o;    o = align16(o + (uint64_t)kMutCols * ((uint64_t)L.n_blocks + 1) * sizeof(int64_t));
+  L.totals = o;  o = align16(o + kMutCols * sizeof(uint64_t));
+  L.end = o;
+  return L;
+}
+// the run's work buffer: the directory -- the exec rows' slots, then each map's upserted rows' slots
+struct MutRunLayout {
+  uint64_t dir_exec, dir[CRR_MUTATION_MAPS], end;
+};
+static MutRunLayout carve_mut_run(const crr_mutation_sizes& P) {
+  MutRunLayout L;
+  uint64_t o = 0;
+  L.dir_exec = o;  o = align16(o + P.n_exec * sizeof(uint64_t));
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) { L.dir[t] = o; o = align16(o + P.n_upsert[t] * sizeof(uint64_t)); }
+  L.end = o;
+  return L;
+}
+
+size_t crr_load_mutation_scratch_bytes(uint32_t n_tasks) { return (size_t)carve_mut_plan(n_tasks).end; }
+
+int crr_load_mutation_plan(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                           const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                           const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                           const crr_ndc_route* routes, const crr_load_branches* branches,
+                           const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
+                           const crr_outputs* replay_out, const uint32_t* position, crr_mutation_row* rows,
+                           void* work, size_t work_bytes, crr_mutation_sizes* plan, void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  if (!plan || store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                           ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (n_tasks && (!rows || !work || ((uintptr_t)work & 15u) || ((uintptr_t)rows & 3u))) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  const MutPlanLayout L = carve_mut_plan(n_tasks);
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  plan->work_needed = L.end;
+  if (n_tasks == 0) return 0;
+  if (L.end > work_bytes) {
+    plan->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    return 0;
+  }
+  int64_t* sums = reinterpret_cast<int64_t*>(static_cast<uint8_t*>(work) + L.sums);
+  uint64_t* totals = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(work) + L.totals);
+  hipLaunchKernelGGL(load_mutation_count_kernel, dim3(L.n_blocks), dim3(kBlock), 0, s, c, a, after, rows, sums, L.n_blocks);
+  hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, sums, L.n_blocks, kMutCols, totals);
+  hipLaunchKernelGGL(load_mutation_offsets_kernel, dim3(L.n_blocks), dim3(kBlock), 0, s, rows, n_tasks, sums, L.n_blocks);
+  hipError_t e;
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[kMutCols];
+  if ((e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  plan->n_exec = h[0];
+  bool fits = true;
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+    plan->n_upsert[t] = h[1 + 2 * t];
+    plan->n_delete[t] = h[2 + 2 * t];
+    fits = fits && h[1 + 2 * t] <= 0xFFFFFFFFull && h[2 + 2 * t] <= 0xFFFFFFFFull;
+  }
+  plan->run_work_needed = carve_mut_run(*plan).end;
+  return fits ? 0 : -1;
+}
+
+int crr_load_mutation_run(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                          const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                          const crr_last_event* last_events, const crr_ndc_result* results, const crr_ndc_route* routes,
+                          const crr_load_branches* branches, const crr_load_ndc_sizes* ndc_plan_host,
+                          const crr_inputs* replay_in, const crr_outputs* replay_out, const uint32_t* position,
+                          const crr_mutation_row* rows, const crr_mutation_sizes* plan_host, const crr_mutation_out* out,
+                          void* work, size_t work_bytes, void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  if (!plan_host || plan_host->err != 0 || !out) return -1;
+  const crr_mutation_sizes& P = *plan_host;
+  const uint32_t n_tasks = P.n_tasks;
+  if (store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                  ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (n_tasks && !rows) return -1;
+  // every total is a sum of 32-bit counts over at most n_tasks tasks, and none exists without an exec row
+  if (P.n_exec > n_tasks || (P.n_exec && !replay_out)) return -1;
+  auto usable = [](const void* p, uint64_t capacity, uint64_t total) {
+    return capacity >= total && (total == 0 || (p && !((uintptr_t)p & 7u)));
+  };
+  if (!usable(out->exec, out->exec_capacity, P.n_exec)) return -1;
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+    if (P.n_upsert[t] > 0xFFFFFFFFull || P.n_delete[t] > 0xFFFFFFFFull) return -1;
+    if ((P.n_upsert[t] || P.n_delete[t]) && !P.n_exec) return -1;
+    if (!usable(out->upsert[t], out->upsert_capacity[t], P.n_upsert[t])) return -1;
+    if (!usable(out->deleted[t], out->delete_capacity[t], P.n_delete[t])) return -1;
+  }
+  const MutRunLayout L = carve_mut_run(P);
+  if (L.end > work_bytes || (L.end && (!work || ((uintptr_t)work & 15u)))) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_tasks == 0 || P.n_exec == 0) return 0;
+  const void* tables[CRR_MUTATION_MAPS] = {replay_out->act, replay_out->timer, replay_out->child, replay_out->rc, replay_out->sig};
+  MutDst d;
+  memset(&d, 0, sizeof d);
+  uint8_t* w = static_cast<uint8_t*>(work);
+  d.dir_exec = reinterpret_cast<uint64_t*>(w + L.dir_exec);
+  d.n_exec = P.n_exec;
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+    if (P.n_upsert[t] && !tables[t]) return -1;
+    d.dir[t] = reinterpret_cast<uint64_t*>(w + L.dir[t]);
+    d.keys[t] = out->deleted[t];
+    d.base[t] = static_cast<const uint8_t*>(tables[t]);
+    d.n_upsert[t] = P.n_upsert[t];
+    d.n_delete[t] = P.n_delete[t];
+  }
+  hipError_t e;
+  if ((e = hipMemsetAsync(work, 0xFF, (size_t)L.end, s)) != hipSuccess) return (int)e;   // kMutNoSlot everywhere
+  hipLaunchKernelGGL(load_mutation_emit_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, a, after, rows, d);
+  auto gather = [&](const void* table, const uint64_t* dir, uint32_t row_bytes, uint64_t n_rows, void* dst) {
+    const uint32_t words = row_bytes / 8;
+    const uint64_t n_words = n_rows * words, blocks = (n_words + kBlock - 1) / kBlock;   // < 2^32 * 26 / 128
+    if (n_words == 0) return;
+    hipLaunchKernelGGL(load_mutation_gather_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s,
+                       static_cast<const uint64_t*>(table), dir, words, n_words, static_cast<uint64_t*>(dst));
+  };
+  gather(replay_out->exec, d.dir_exec, sizeof(crr_exec_row), P.n_exec, out->exec);
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) gather(tables[t], d.dir[t], kRowBytes[t], P.n_upsert[t], out->upsert[t]);
   return (int)hipGetLastError();
 }
 

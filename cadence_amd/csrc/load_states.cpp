@@ -5,7 +5,8 @@
 // crr_load_states_verify_host (include/cadence_load_verify.h) runs the same load, then load_decode.h's verify_wf;
 // crr_load_branches_host (include/cadence_load_ndc.h) the same load, then its branch walk;
 // crr_load_store_checksums_host (include/cadence_load_store.h) both, then load_decode.h's store_task per task;
-// crr_load_store_vh_host (include/cadence_load_store_vh.h) the same, then its sizes and its sequential blob writer.
+// crr_load_store_vh_host (include/cadence_load_store_vh.h) the same, then its sizes and its sequential blob writer;
+// crr_load_mutation_host (include/cadence_load_mutation.h) the same, then its count and emit passes and the gather.
 #include <stdlib.h>
 
 #include <thread>
@@ -284,6 +285,111 @@ extern "C" int crr_load_store_vh_host(const crr_state_batch* in, const crr_repl_
     }
   }
   free(my_rows), free(my_off);
+  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
+  free(k.s);
+  free(c.s);
+  return ret;
+}
+
+// the pending-entry mutation to store for routed tasks (include/cadence_load_mutation.h): the same load, branch walk
+// and decision, load_decode.h's count pass per task, serial prefixes, then its emit pass into a directory of this
+// call and the rows copied through it
+extern "C" int crr_load_mutation_host(const crr_state_batch* in, const crr_repl_task* tasks,
+                                      const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                                      const crr_ndc_route* routes, const crr_load_image* after, crr_mutation_row* rows,
+                                      const crr_mutation_out* out, crr_mutation_sizes* plan, int threads) {
+  if (!in || !plan || (n_tasks && (!tasks || !last_events || !results || !routes))) return -1;
+  if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
+  NdcWork k;
+  if (count_branches(c, threads, k) != 0) {
+    free(c.s);
+    return -2;
+  }
+  StoreIn a;
+  a.tasks = tasks;
+  a.last = last_events;
+  a.results = results;
+  a.routes = routes;
+  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
+  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
+  a.n_tasks = n_tasks;
+  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
+  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
+  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
+  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
+  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
+  crr_mutation_row* my_rows = static_cast<crr_mutation_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_mutation_row)));
+  uint64_t* dir[1 + CRR_MUTATION_MAPS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int ret = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current && my_rows ? 0 : -2;
+  if (ret == 0) {
+    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
+    const ImageAfter img = {after, n_wf};
+    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { mutation_count_task(c, a, img, i, my_rows[i]); });
+    memset(plan, 0, sizeof *plan);
+    plan->n_tasks = n_tasks;
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+      crr_mutation_row& o = my_rows[i];
+      if (o.exec_index != 0xFFFFFFFFu) o.exec_index = (uint32_t)plan->n_exec++;
+      for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+        o.map[t].upsert_begin = (uint32_t)plan->n_upsert[t];
+        o.map[t].delete_begin = (uint32_t)plan->n_delete[t];
+        plan->n_upsert[t] += o.map[t].n_upsert;
+        plan->n_delete[t] += o.map[t].n_delete;
+      }
+    }
+    uint64_t dir_bytes = align16(plan->n_exec * sizeof(uint64_t));
+    for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+      dir_bytes += align16(plan->n_upsert[t] * sizeof(uint64_t));
+      if (plan->n_upsert[t] > 0xFFFFFFFFull || plan->n_delete[t] > 0xFFFFFFFFull) ret = -1;
+    }
+    plan->run_work_needed = dir_bytes;
+    if (out && ret == 0) {
+      auto usable = [](const void* p, uint64_t capacity, uint64_t total) { return capacity >= total && (total == 0 || p); };
+      bool ok = usable(out->exec, out->exec_capacity, plan->n_exec);
+      for (int t = 0; t < CRR_MUTATION_MAPS; ++t)
+        ok = ok && usable(out->upsert[t], out->upsert_capacity[t], plan->n_upsert[t]) &&
+             usable(out->deleted[t], out->delete_capacity[t], plan->n_delete[t]);
+      if (!ok) ret = -1;   // nothing written
+    }
+    if (ret == 0 && rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_mutation_row));
+    if (ret == 0 && out && plan->n_exec) {
+      MutDst d;
+      memset(&d, 0, sizeof d);
+      d.n_exec = plan->n_exec;
+      dir[0] = static_cast<uint64_t*>(malloc((size_t)plan->n_exec * sizeof(uint64_t)));
+      bool ok = dir[0] != nullptr;
+      for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+        dir[1 + t] = static_cast<uint64_t*>(malloc(((size_t)plan->n_upsert[t] + 1) * sizeof(uint64_t)));
+        ok = ok && dir[1 + t];
+        d.dir[t] = dir[1 + t];
+        d.keys[t] = out->deleted[t];
+        d.base[t] = static_cast<const uint8_t*>(after->rows[t]);
+        d.n_upsert[t] = plan->n_upsert[t];
+        d.n_delete[t] = plan->n_delete[t];
+      }
+      d.dir_exec = dir[0];
+      if (!ok) {
+        ret = -2;
+      } else {
+        memset(dir[0], 0xFF, (size_t)plan->n_exec * sizeof(uint64_t));
+        for (int t = 0; t < CRR_MUTATION_MAPS; ++t) memset(dir[1 + t], 0xFF, (size_t)plan->n_upsert[t] * sizeof(uint64_t));
+        parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { mutation_emit_task(c, a, img, i, my_rows, d); });
+        auto gather = [&](const void* table, const uint64_t* dr, uint32_t row_bytes, uint64_t n_rows, void* dst) {
+          const uint32_t words = row_bytes / 8;
+          uint64_t* q = static_cast<uint64_t*>(dst);
+          for (uint64_t g = 0; g < n_rows * words; ++g) q[g] = mutation_gather_word(static_cast<const uint64_t*>(table), dr, words, g);
+        };
+        gather(after->exec, d.dir_exec, sizeof(crr_exec_row), plan->n_exec, out->exec);
+        for (int t = 0; t < CRR_MUTATION_MAPS; ++t) gather(after->rows[t], d.dir[t], kRowBytes[t], plan->n_upsert[t], out->upsert[t]);
+      }
+    }
+  }
+  for (uint64_t* p : dir) free(p);
+  free(my_rows);
   free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
   free(k.s);
   free(c.s);

@@ -25,6 +25,10 @@ after materialising a state -- the stored ``checksum.Checksum`` against a freshl
 ``StateLoader.store_checksums`` / ``store_checksums_host`` give, per routed task, the checksum Go stores with the
 state when it commits the task (``include/cadence_load_store.h``): from the rows the resumed replay left for a
 task applied to the current branch, from the loaded image for one backfilled onto another branch.
+
+``StateLoader.mutation`` / ``mutation_host`` give, per routed task, what else that commit writes
+(``include/cadence_load_mutation.h``): the post-replay exec row, the pending entries to upsert and the keys to
+delete; ``apply_mutation`` applies such a result to the persisted blobs as a host shim would.
 """
 from __future__ import annotations
 
@@ -469,6 +473,8 @@ def _host_lib():
         L.crr_load_store_checksums_host.restype = ctypes.c_int
         L.crr_load_store_vh_host.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, ctypes.c_int]
         L.crr_load_store_vh_host.restype = ctypes.c_int
+        L.crr_load_mutation_host.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+        L.crr_load_mutation_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -656,6 +662,199 @@ def store_version_histories_host(sbs: StateBlobSet, tasks, last_events, results,
     return rows, off, out[:int(P.n_bytes)].copy()
 
 
+# ---- the pending-entry mutation to store with them (include/cadence_load_mutation.h) ----------------------------
+@dataclasses.dataclass
+class Mutation:
+    """What ``crr_load_mutation_run`` wrote: per task a row (``abi.MUTATION_ROW``), the exec rows of the APPLIED tasks
+    dense in task order, and per pending map (``abi.MUTATION_MAPS``) the upserted rows and the deleted keys."""
+    rows: np.ndarray                     # abi.MUTATION_ROW [n_tasks]
+    exec: np.ndarray                     # abi.EXEC_ROW [n_exec]
+    upsert: Dict[str, np.ndarray]        # map name -> its row dtype
+    deleted: Dict[str, np.ndarray]       # map name -> int64 keys (a timer's interned TimerID widened)
+
+    def exec_of(self, k: int):
+        """Task k's post-replay exec row, None when it has none."""
+        i = int(self.rows[k]["exec_index"])
+        return None if i == abi.MUTATION_NO_EXEC else self.exec[i]
+
+    def upserts(self, k: int, name: str) -> np.ndarray:
+        m = self.rows[k]["map"][abi.MUTATION_MAPS.index(name)]
+        return self.upsert[name][int(m["upsert_begin"]):int(m["upsert_begin"]) + int(m["n_upsert"])]
+
+    def deletes(self, k: int, name: str) -> np.ndarray:
+        m = self.rows[k]["map"][abi.MUTATION_MAPS.index(name)]
+        return self.deleted[name][int(m["delete_begin"]):int(m["delete_begin"]) + int(m["n_delete"])]
+
+    @property
+    def n_bytes(self) -> int:
+        """The bytes that cross to the host: the rows, the exec rows, the upserted rows and the keys."""
+        return int(self.rows.nbytes + self.exec.nbytes + sum(a.nbytes for a in self.upsert.values()) +
+                   sum(a.nbytes for a in self.deleted.values()))
+
+    def image_bytes(self) -> Dict[str, bytes]:
+        out = {"rows": self.rows.tobytes(), "exec": self.exec.tobytes()}
+        out.update({"upsert." + n: self.upsert[n].tobytes() for n in abi.MUTATION_MAPS})
+        out.update({"deleted." + n: self.deleted[n].tobytes() for n in abi.MUTATION_MAPS})
+        return out
+
+
+def _mutation_buffers(P: abi.CMutationSizes):
+    """Host buffers of exactly the plan's totals and the ``crr_mutation_out`` over them."""
+    ex = np.zeros(int(P.n_exec), abi.EXEC_ROW)
+    up = {n: np.zeros(int(P.n_upsert[t]), _ROW_DTYPES[n]) for t, n in enumerate(abi.MUTATION_MAPS)}
+    de = {n: np.zeros(int(P.n_delete[t]), np.int64) for t, n in enumerate(abi.MUTATION_MAPS)}
+    o = abi.CMutationOut()
+    o.exec, o.exec_capacity = (ex.ctypes.data if ex.size else None), ex.shape[0]
+    for t, n in enumerate(abi.MUTATION_MAPS):
+        o.upsert[t], o.upsert_capacity[t] = (up[n].ctypes.data if up[n].size else None), up[n].shape[0]
+        o.deleted[t], o.delete_capacity[t] = (de[n].ctypes.data if de[n].size else None), de[n].shape[0]
+    return ex, up, de, o
+
+
+def mutation_host(sbs: StateBlobSet, tasks, last_events, results, routes, after: Optional[LoadedStates] = None,
+                  threads: int = 1) -> Mutation:
+    """The pending-entry mutation to store with each task's state once the task is committed, by the host restatement
+    (``crr_load_mutation_host``), arguments as ``store_checksums_host``."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
+    img, _keep = _after_image(after, sbs.n_wf)
+    n = int(tasks.shape[0])
+    P = abi.CMutationSizes()
+
+    def ptr(a):
+        return a.ctypes.data if a.size else None
+
+    def call(rows, out):
+        rc = L.crr_load_mutation_host(ctypes.byref(c), ptr(tasks), ptr(last), n, ptr(results), ptr(routes),
+                                      ctypes.byref(img) if img is not None else None, rows, out, ctypes.byref(P), threads)
+        if rc != 0:
+            raise RuntimeError(f"crr_load_mutation_host failed: {rc}")
+    call(None, None)   # sizes
+    rows = np.zeros(n, abi.MUTATION_ROW)
+    ex, up, de, o = _mutation_buffers(P)
+    call(ptr(rows), ctypes.byref(o))
+    return Mutation(rows, ex, up, de)
+
+
+def _struct_fields(raw: bytes) -> Dict[int, bytes]:
+    """The top-level fields of a thrift-binary struct whose fields are scalars, binaries, list<binary> or
+    map<binary, binary> (the six state structs): field id -> the bytes of a binary field, b"" for any other."""
+    size = {2: 1, 3: 1, 4: 8, 6: 2, 8: 4, 10: 8}
+    out, p = {}, 0
+
+    def binary(p):
+        n = struct.unpack_from(">i", raw, p)[0]
+        return raw[p + 4:p + 4 + n], p + 4 + n
+    while raw[p] != 0:
+        t, fid = raw[p], struct.unpack_from(">h", raw, p + 1)[0]
+        p += 3
+        out[fid] = b""
+        if t in size:
+            p += size[t]
+        elif t == T_STRING:
+            out[fid], p = binary(p)
+        elif t == T_LIST and raw[p] == T_STRING:
+            n = struct.unpack_from(">i", raw, p + 1)[0]
+            p += 5
+            for _ in range(n):
+                p = binary(p)[1]
+        elif t == T_MAP and raw[p] == T_STRING and raw[p + 1] == T_STRING:
+            n = struct.unpack_from(">i", raw, p + 2)[0]
+            p += 6
+            for _ in range(2 * n):
+                p = binary(p)[1]
+        else:
+            raise ValueError(f"field {fid}: type {t} is not one the state structs use")
+    return out
+
+
+_MAP_KIND = {"act": abi.STATE_ACTIVITY, "timer": abi.STATE_TIMER, "child": abi.STATE_CHILD, "rc": abi.STATE_REQUEST_CANCEL,
+             "sig": abi.STATE_SIGNAL}
+
+
+def apply_mutation(sbs: StateBlobSet, tasks, mutation: Mutation, vh_blobs, checksums, names, reset_points=None) -> StateBlobSet:
+    """What a host shim does with the device's result: the store after every generated task's write.  For each task
+    whose outcome is ``APPLIED`` or ``BACKFILLED`` its state's blobs (other states are kept as they are): the
+    entries whose keys the mutation deletes dropped, the blobs of the upserted rows replaced or added (encoded with
+    ``activity_values`` / ``timer_values`` / ``child_values`` / ``initiated_values``), and the execution blob written
+    again -- from the gathered exec row for an APPLIED task -- with the task's ``VersionHistories`` blob as field 122.
+    ``vh_blobs``: ``store_version_histories``' ``(rows, blob_off, bytes)``; ``checksums``: ``store_checksums``' rows
+    (all three results must agree on every outcome); ``names``: per workflow its key dictionary after the task,
+    ``{key id: string}`` or the interner ``{string: key id}``.  ``reset_points``: ``{workflow: [(binary checksum,
+    resettable)]}`` for the tasks flagged ``MUTATION_RESET_POINTS_CHANGED`` (the reset-point rows are not part of
+    the mutation); the others keep their stored ``AutoResetPoints``.  A state with more than one generated task takes
+    the last one's write."""
+    tasks = np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
+    vh_rows, vh_off, vh_bytes = vh_blobs
+    rows = mutation.rows
+    if not ((rows["outcome"] == vh_rows["outcome"]).all() and (rows["outcome"] == checksums["outcome"]).all()):
+        raise ValueError("the mutation, the VersionHistories blobs and the checksums disagree on an outcome")
+    states = []
+    for w in range(sbs.n_wf):
+        b0, nb = int(sbs.wf["blob_begin"][w]), int(sbs.wf["blob_count"][w])
+        blobs = []
+        for b in range(b0, b0 + nb):
+            B = sbs.blob[b]
+            s = sbs.strings[int(B["str_off"]):int(B["str_off"]) + int(B["str_len"])].tobytes().decode()
+            blobs.append((int(B["kind"]), int(B["id"]), int(B["aux_time"]), s, sbs.blob_bytes(b)))
+        states.append([int(sbs.wf["next_event_id"][w]), blobs])
+    for k in range(tasks.shape[0]):
+        outcome = int(rows[k]["outcome"])
+        if outcome not in (abi.StoreOutcome.APPLIED, abi.StoreOutcome.BACKFILLED):
+            continue
+        w = int(tasks[k]["wf"])
+        key_names = names[w]
+        if any(isinstance(x, str) for x in key_names):
+            key_names = _inverse(key_names)
+        blobs = states[w][1]
+        vh = bytes(vh_bytes[int(vh_off[k]):int(vh_off[k + 1])])
+        ei = [i for i, b in enumerate(blobs) if b[0] == abi.STATE_EXECUTION][0]
+        old = _struct_fields(blobs[ei][4])
+        if outcome == abi.StoreOutcome.BACKFILLED:   # only field 122 changes: the blob's other bytes are kept
+            raw = blobs[ei][4]
+            at = raw.index(struct.pack(">bhi", T_STRING, 122, len(old[122])) + old[122])
+            blobs[ei] = blobs[ei][:4] + (raw[:at] + struct.pack(">bhi", T_STRING, 122, len(vh)) + vh + raw[at + 7 + len(old[122]):],)
+            continue
+        ex = mutation.exec_of(k)
+        v = execution_values(ex, old[104], [], [])
+        v["VersionHistories"] = vh
+        if int(rows[k]["flags"]) & abi.MUTATION_RESET_POINTS_CHANGED:
+            if reset_points is None or w not in reset_points:
+                raise ValueError(f"task {k}: the reset points of workflow {w} changed and none were given")
+            v["AutoResetPoints"] = encode_reset_points(reset_points[w])
+        else:
+            v["AutoResetPoints"] = old[115]
+        blobs[ei] = (abi.STATE_EXECUTION, 0, 0, "", encode_struct("WorkflowExecutionInfo", v))
+        states[w][0] = int(ex["next_event_id"])
+        for name in abi.MUTATION_MAPS:
+            kind = _MAP_KIND[name]
+
+            def key_of(b, timer=name == "timer"):
+                return b[3] if timer else b[1]
+            gone = set(key_names[int(x)] if name == "timer" else int(x) for x in mutation.deletes(k, name))
+            fresh = {}
+            for r in mutation.upserts(k, name):
+                if name == "act":
+                    fresh[int(r["schedule_id"])] = (kind, int(r["schedule_id"]), to_unix_nano(r["last_heartbeat_time"]), "",
+                                                    encode_struct("ActivityInfo", activity_values(r, key_names[int(r["key"])])))
+                elif name == "timer":
+                    fresh[key_names[int(r["key"])]] = (kind, 0, 0, key_names[int(r["key"])], encode_struct("TimerInfo", timer_values(r)))
+                elif name == "child":
+                    fresh[int(r["initiated_id"])] = (kind, int(r["initiated_id"]), 0, "", encode_struct("ChildExecutionInfo", child_values(r)))
+                else:
+                    fresh[int(r["initiated_id"])] = (kind, int(r["initiated_id"]), 0, "", encode_struct(
+                        "SignalInfo" if name == "sig" else "RequestCancelInfo", initiated_values(r, name == "sig")))
+            kept = []
+            for b in blobs:   # REPLACE per upserted entry, then DELETE per deleted key (workflowStateMaps.go)
+                if b[0] != kind:
+                    kept.append(b)
+                elif key_of(b) not in gone:
+                    kept.append(fresh.pop(key_of(b), b))
+            blobs[:] = kept + [b for key, b in fresh.items() if key not in gone]
+    return build_blob_set([(nei, blobs) for nei, blobs in states])
+
+
 def apply_mask(routes: np.ndarray, tasks: Optional[np.ndarray] = None, n_wf: Optional[int] = None) -> np.ndarray:
     """The workflows whose task is to be replayed onto the placed rows (``ROUTE_APPLY_CURRENT``), as
     ``LoadedImage.resumable(mask=...)`` takes them (canonical workflow order; ``replication.BlobReplication``'s
@@ -733,6 +932,12 @@ class StateLoader:
         L.crr_load_store_vh_plan.restype = ctypes.c_int
         L.crr_load_store_vh_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 11 + [ctypes.c_size_t, vp]
         L.crr_load_store_vh_run.restype = ctypes.c_int
+        L.crr_load_mutation_scratch_bytes.argtypes = [ctypes.c_uint32]
+        L.crr_load_mutation_scratch_bytes.restype = ctypes.c_size_t
+        L.crr_load_mutation_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32] + [vp] * 9 + [ctypes.c_size_t, vp, vp]
+        L.crr_load_mutation_plan.restype = ctypes.c_int
+        L.crr_load_mutation_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 11 + [ctypes.c_size_t, vp]
+        L.crr_load_mutation_run.restype = ctypes.c_int
         self.last_ndc = None
         self.scratch = None
         self.scratch_bytes = 0
@@ -999,6 +1204,95 @@ class StateLoader:
             return T["rows"], T["blob_off"], out
         return (T["rows"][:n * abi.VH_BLOB_ROW.itemsize].cpu().numpy().view(abi.VH_BLOB_ROW).copy(),
                 T["blob_off"].cpu().numpy().view(np.uint64).copy(), out[:int(plan.sizes.n_bytes)].cpu().numpy().copy())
+
+    # ---- include/cadence_load_mutation.h -------------------------------------------------------------------
+    def mutation_plan(self, ds: DeviceStates, tasks, last_events, db=None, perm=None) -> "MutationPlan":
+        """Decide, classify and count (``crr_load_mutation_plan``, one synchronisation): the rows stay on the device,
+        ``plan.sizes`` holds the totals ``mutation_run`` will write.  Arguments as ``store_checksums``."""
+        n, T, head, tail = self._store_args(ds, tasks, last_events, db, perm, "mutation")
+        torch, dev = self.torch, self.engine.dev
+        work_bytes = int(self.lib.crr_load_mutation_scratch_bytes(n))
+        T["rows"] = torch.empty(max(n, 1) * abi.MUTATION_ROW.itemsize, dtype=torch.uint8, device=dev)
+        T["work"] = torch.empty(work_bytes + 16, dtype=torch.uint8, device=dev)
+        P = abi.CMutationSizes()
+        rc = self.lib.crr_load_mutation_plan(*head, n, *tail, ctypes.c_void_p(T["rows"].data_ptr()),
+                                             ctypes.c_void_p(T["work"].data_ptr()), ctypes.c_size_t(work_bytes),
+                                             ctypes.byref(P), self._stream())
+        if rc != 0 or P.err != 0:
+            raise RuntimeError(f"crr_load_mutation_plan failed: {rc} (err {P.err})")
+        return MutationPlan(n, P, T, head, tail)
+
+    def mutation_run(self, plan: "MutationPlan", out=None, capacity=None):
+        """Write the planned mutation (``crr_load_mutation_run``, enqueued on the current stream).  ``out``: device
+        uint8 tensors (8-byte aligned) by ``"exec"``, ``"upsert.<map>"`` and ``"deleted.<map>"`` (default: each of
+        exactly the plan's total); ``capacity``: rows / keys that may be written, by the same names (default: what the
+        tensor holds).  Returns the tensors.  Too small a capacity raises and launches nothing."""
+        torch, dev, P = self.torch, self.engine.dev, plan.sizes
+        item = {"exec": abi.EXEC_ROW.itemsize}
+        total = {"exec": int(P.n_exec)}
+        for t, name in enumerate(abi.MUTATION_MAPS):
+            item["upsert." + name], total["upsert." + name] = _ROW_DTYPES[name].itemsize, int(P.n_upsert[t])
+            item["deleted." + name], total["deleted." + name] = 8, int(P.n_delete[t])
+        out = dict(out or {})
+        for f in item:
+            if f not in out:
+                out[f] = torch.empty(max(total[f], 1) * item[f], dtype=torch.uint8, device=dev)
+        cap = {f: int(out[f].numel()) // item[f] for f in item}
+        cap.update(capacity or {})
+        o = abi.CMutationOut()
+        o.exec, o.exec_capacity = out["exec"].data_ptr(), cap["exec"]
+        for t, name in enumerate(abi.MUTATION_MAPS):
+            o.upsert[t], o.upsert_capacity[t] = out["upsert." + name].data_ptr(), cap["upsert." + name]
+            o.deleted[t], o.delete_capacity[t] = out["deleted." + name].data_ptr(), cap["deleted." + name]
+        T = plan.tensors
+        need = int(P.run_work_needed)
+        if int(T["work"].numel()) < need + 16:
+            T["work"] = torch.empty(need + 16, dtype=torch.uint8, device=dev)
+        rc = self.lib.crr_load_mutation_run(*plan.head, *plan.tail, ctypes.c_void_p(T["rows"].data_ptr()), ctypes.byref(P),
+                                            ctypes.byref(o), ctypes.c_void_p(T["work"].data_ptr()), ctypes.c_size_t(need),
+                                            self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_mutation_run failed: {rc}")
+        T["out"] = out
+        self.last_mutation = plan   # alive until the stream has run the kernels
+        return out
+
+    def mutation(self, ds: DeviceStates, tasks, last_events, db=None, perm=None, on_device: bool = False):
+        """The pending-entry mutation to store with each task's state once the task is committed
+        (include/cadence_load_mutation.h), for the tasks the last ``ndc_prepare`` decided; arguments as
+        ``store_checksums``, whose outcome and status every row repeats.  Returns ``(rows abi.MUTATION_ROW[n], Mutation)``
+        -- the Mutation's per-task, per-map views are ``exec_of`` / ``upserts`` / ``deletes``.  ``on_device``: ``(the
+        rows as a device byte tensor, the output tensors by name, the plan)``, nothing more copied back."""
+        plan = self.mutation_plan(ds, tasks, last_events, db=db, perm=perm)
+        out = self.mutation_run(plan)
+        if on_device:
+            return plan.tensors["rows"], out, plan
+        m = plan.download(out)
+        return m.rows, m
+
+
+@dataclasses.dataclass
+class MutationPlan:
+    """A finished ``crr_load_mutation_plan``: the host sizes, the device rows and work buffer and the arguments of the
+    call, which ``crr_load_mutation_run`` takes again."""
+    n: int
+    sizes: abi.CMutationSizes
+    tensors: Dict[str, object]
+    head: tuple
+    tail: tuple
+
+    def rows(self) -> np.ndarray:
+        return self.tensors["rows"][:self.n * abi.MUTATION_ROW.itemsize].cpu().numpy().view(abi.MUTATION_ROW).copy()
+
+    def download(self, out) -> Mutation:
+        """The run's output tensors copied to the host: exactly the plan's totals of each."""
+        P = self.sizes
+
+        def host(f, dt, k):
+            return out[f][:k * np.dtype(dt).itemsize].cpu().numpy().view(dt).copy()
+        return Mutation(self.rows(), host("exec", abi.EXEC_ROW, int(P.n_exec)),
+                        {n: host("upsert." + n, _ROW_DTYPES[n], int(P.n_upsert[t])) for t, n in enumerate(abi.MUTATION_MAPS)},
+                        {n: host("deleted." + n, np.int64, int(P.n_delete[t])) for t, n in enumerate(abi.MUTATION_MAPS)})
 
 
 @dataclasses.dataclass
