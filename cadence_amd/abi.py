@@ -390,6 +390,21 @@ class CMutationOut(ctypes.Structure):
                 ("deleted", ctypes.c_void_p * 5), ("delete_capacity", ctypes.c_uint64 * 5)]
 
 
+# ---- the execution blob to store for routed tasks (include/cadence_load_store_exec.h) ----------------------
+EXEC_BLOB_TASK = np.dtype([("now_ns", "<i8"), ("history_size_delta", "<i8")])
+EXEC_BLOB_ROW = np.dtype([("outcome", "<i4"), ("status", "<i4"), ("flags", "<u4"), ("len", "<u4"), ("next_event_id", "<i8")])
+EXEC_BLOB_HOST_RESET_POINTS = 1               # CRR_EXEC_BLOB_HOST_*: why a generated task's blob is left to the host
+EXEC_BLOB_HOST_SEARCH_ATTRIBUTES = 2
+EXEC_BLOB_HOST_REQUEST_ID = 4
+EXEC_BLOB_HOST_STORED_SHAPE = 8
+
+
+class CExecBlobSizes(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_int32), ("n_tasks", ctypes.c_uint32), ("n_bytes", ctypes.c_uint64),
+                ("n_blobs", ctypes.c_uint64), ("n_host", ctypes.c_uint64), ("work_needed", ctypes.c_uint64),
+                ("run_work_needed", ctypes.c_uint64)]
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -460,11 +475,11 @@ def check_layout(lib):
     for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize),
                  (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize),
                  (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize), (30, VH_BLOB_ROW.itemsize),
-                 (33, MUTATION_ROW.itemsize)):
+                 (33, MUTATION_ROW.itemsize), (36, EXEC_BLOB_TASK.itemsize), (37, EXEC_BLOB_ROW.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
     for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage),
                   (24, CLoadBranches), (25, CLoadNdcSizes), (31, CVhBlobSizes), (34, CMutationSizes),
-                  (35, CMutationOut)):
+                  (35, CMutationOut), (38, CExecBlobSizes)):
         if lib.crr_sizeof(i) != ctypes.sizeof(st):
             raise RuntimeError(f"ABI layout mismatch for {st.__name__}: C {lib.crr_sizeof(i)} vs ctypes {ctypes.sizeof(st)}")

@@ -9,6 +9,7 @@
 #include "cadence_load_ndc.h"
 #include "cadence_load_mutation.h"
 #include "cadence_load_store.h"
+#include "cadence_load_store_exec.h"
 #include "cadence_load_store_vh.h"
 #include "cadence_load_verify.h"
 #include "cadence_replay.h"
@@ -276,6 +277,9 @@ size_t crr_sizeof(int which) {
     case 33: return sizeof(crr_mutation_row);
     case 34: return sizeof(crr_mutation_sizes);
     case 35: return sizeof(crr_mutation_out);
+    case 36: return sizeof(crr_exec_blob_task);
+    case 37: return sizeof(crr_exec_blob_row);
+    case 38: return sizeof(crr_exec_blob_sizes);
     default: return 0;
   }
 }

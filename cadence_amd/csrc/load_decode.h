@@ -22,6 +22,9 @@
 //   mutation_count_task / mutation_emit_task   per task  (on request, cadence_load_mutation.h) the pending entries
 //                              to upsert and the keys to delete for the same decision: one merge walk per pending
 //                              map (mutation_walk) over the loaded image before and the state view after
+//   exec_plan_task / exec_walk / exec_emit_chunk   per task  (on request, cadence_load_store_exec.h) the execution blob
+//                              to store for the same decision: the stored blob's top-level fields spliced with the
+//                              task's overrides, through an emitter (an edit script, or the sequential byte sink)
 //
 // Wire format: thrift binary (big-endian; field header = type byte + i16 id, 0 ends a struct), field IDs of
 // .gen/go/sqlblobs/sqlblobs.go restated below (tests/golden/sqlblobs_fields.json pins them); a field whose
@@ -39,6 +42,7 @@
 #include "cadence_load_store.h"
 #include "cadence_load_mutation.h"
 #include "cadence_load_store_vh.h"
+#include "cadence_load_store_exec.h"
 #include "cadence_load_verify.h"
 
 #if defined(__HIPCC__)
@@ -1902,6 +1906,481 @@ CRR_HD void mutation_emit_task(const Ctx& c, const StoreIn& a, const After& afte
 CRR_HD uint64_t mutation_gather_word(const uint64_t* table, const uint64_t* dir, uint32_t words, uint64_t g) {
   const uint64_t src = dir[g / words];
   return src == kMutNoSlot ? 0ull : table[src * words + g % words];
+}
+
+// ---- per task: the execution blob to store (cadence_load_store_exec.h) ------------------------------------------
+// CloseTransactionAsMutation always writes ExecutionInfo (mutable_state_builder.go:3998-3999).  Every thrift scalar
+// is fixed-width and thriftrw writes the set fields in ascending id, so the blob to store is the stored blob with a
+// bounded number of edits: the decision (exec_plan_task) and the edit rules (exec_walk) are written once; the walk
+// takes an emitter -- the edit script the device's emit kernel reads, or the sequential ByteSink of the host.
+constexpr int kExecSegs = 48, kExecPatches = 24, kExecFields = 25;
+constexpr uint32_t kSegStored = 0, kSegVh = 1, kSegTask = 2, kSegLit = 3;
+constexpr uint32_t kSegLenMask = 0x3FFFFFFFu;
+
+struct ExecSeg {
+  uint32_t dst;        // offset in the new blob
+  uint32_t len_kind;   // length in the low 30 bits, the source kind above
+  uint64_t src;        // offset into the source's buffer; a literal: its (at most 8) bytes, the first one lowest
+};
+struct ExecPatch {
+  uint32_t dst, width;   // `width` (1, 4 or 8) bytes at dst ...
+  uint64_t value;        // ... are this value, big-endian
+};
+struct ExecScript {
+  uint32_t n_seg, n_patch, len, reserved;
+  ExecSeg seg[kExecSegs];       // ascending by dst, contiguous from 0 to len
+  ExecPatch patch[kExecPatches];
+};
+static_assert(sizeof(ExecScript) == 16 + 16 * kExecSegs + 16 * kExecPatches, "scripts are packed, 16-byte aligned");
+
+// the overridden fields in ascending id: slot <-> field id, and each slot's thrift type
+CRR_HD int exec_slot_of(int id) {
+  switch (id) {
+    case 18: return 0;   case 34: return 1;   case 36: return 2;   case 48: return 3;   case 50: return 4;
+    case 52: return 5;   case 56: return 6;   case 58: return 7;   case 60: return 8;   case 62: return 9;
+    case 64: return 10;  case 66: return 11;  case 68: return 12;  case 69: return 13;  case 70: return 14;
+    case 71: return 15;  case 74: return 16;  case 78: return 17;  case 80: return 18;  case 106: return 19;
+    case 108: return 20; case 110: return 21; case 112: return 22; case 114: return 23; case 122: return 24;
+    default: return -1;
+  }
+}
+CRR_HD int exec_id_of(int slot) {
+  switch (slot) {
+    case 0: return 18;   case 1: return 34;   case 2: return 36;   case 3: return 48;   case 4: return 50;
+    case 5: return 52;   case 6: return 56;   case 7: return 58;   case 8: return 60;   case 9: return 62;
+    case 10: return 64;  case 11: return 66;  case 12: return 68;  case 13: return 69;  case 14: return 70;
+    case 15: return 71;  case 16: return 74;  case 17: return 78;  case 18: return 80;  case 19: return 106;
+    case 20: return 108; case 21: return 110; case 22: return 112; case 23: return 114; default: return 122;
+  }
+}
+constexpr uint32_t kExecApplied = (1u << kExecFields) - 1u;
+constexpr uint32_t kExecBackfill = (1u << 6) | (1u << 20) | (1u << 24);   // 56, 108, 122
+constexpr uint32_t kExecStrings = (1u << 16) | (1u << 17) | (1u << 21) | (1u << 22) | (1u << 23) | (1u << 24);
+constexpr int kExecSlot18 = 0, kExecSlot74 = 16, kExecSlot108 = 20, kExecSlot122 = 24;
+CRR_HD uint8_t exec_type_of(int slot) {
+  if ((kExecStrings >> slot) & 1u) return T_STRING;
+  if (slot == 14) return T_BOOL;
+  return (slot == 1 || slot == 2 || slot == 10) ? T_I32 : T_I64;
+}
+CRR_HD uint32_t exec_width_of(uint8_t t) { return t == T_BOOL ? 1u : t == T_I32 ? 4u : 8u; }
+CRR_HD int64_t to_unix_nano(int64_t v) { return v == CRR_ZERO_TIME ? kGoZeroTimeNanos : v; }
+
+// what a call reads beside StoreIn: the tasks' clocks, the VersionHistories plan of the same tasks, the tasks' event
+// blobs (optional) and where the event types of this call are (the device: the replay's column; the host: a flag
+// per workflow)
+struct ExecIn {
+  const crr_exec_blob_task* xt;
+  const crr_vh_blob_row* vh_rows;
+  const uint64_t* vh_off;
+  uint64_t vh_total;
+  const uint8_t* tb_bytes;
+  const uint64_t* tb_off;
+  const crr_blob_wf* tb_wf;
+  uint32_t tb_n_blobs, tb_n_wf;
+  const uint8_t* etype;
+  const crr_workflow* ev_wf;
+  uint32_t ev_n_wf, ev_stride, ev_wave_begin;
+  const uint8_t* upserts;
+};
+
+// what the decision leaves for the walk
+struct ExecTask {
+  uint32_t active, seen;   // the slots overridden; those of them the stored blob holds
+  uint32_t exec_blob;      // the execution blob's index in the batch
+  uint32_t vh_len, rq_len;
+  int rq_mode;             // field 74: 0 "emptyUuid", 1 "", 2 the task's bytes at rq_off
+  bool omit18;
+  uint64_t vh_off, rq_off;
+  int64_t now, hist;
+};
+
+CRR_HD int64_t exec_scalar(int slot, const crr_exec_row& R, const ExecTask& T) {
+  switch (slot) {
+    case 0: return R.completion_event_batch_id;
+    case 1: return R.state;
+    case 2: return R.close_status;
+    case 3: return R.last_event_task_id;
+    case 4: return R.last_first_event_id;
+    case 5: return R.last_processed_event;
+    case 6: return T.now;
+    case 7: return R.decision_version;
+    case 8: return R.decision_schedule_id;
+    case 9: return R.decision_started_id;
+    case 10: return R.decision_timeout;
+    case 11: return R.decision_attempt;
+    case 12: return to_unix_nano(R.decision_started_ts);
+    case 13: return to_unix_nano(R.decision_scheduled_ts);
+    case 14: return (R.flags & CRR_EXEC_CANCEL_REQUESTED) ? 1 : 0;
+    case 15: return to_unix_nano(R.decision_orig_scheduled_ts);
+    case 19: return R.signal_count;
+    case 20: return T.hist;
+    default: return 0;   // 80 StickyScheduleToStartTimeout
+  }
+}
+
+// whether the events of this call at exec slot `slot` (the device position; the host: workflow w) hold an
+// UpsertWorkflowSearchAttributes, the events addressed as the replay addresses them
+CRR_HD bool exec_has_upsert(const ExecIn& x, uint64_t slot, uint32_t w) {
+  if (x.upserts) return x.upserts[w] != 0;
+  if (!x.etype || !x.ev_wf || slot >= x.ev_n_wf) return false;
+  const crr_workflow& D = x.ev_wf[slot];
+  const uint64_t st = slot >= x.ev_wave_begin ? 1 : x.ev_stride;
+  for (int32_t s = 0; s < D.ev_count; ++s)
+    if ((x.etype[(uint64_t)D.ev_begin + (uint64_t)s * st] & CRR_ETYPE_MASK) == CRR_EV_UPSERT_WORKFLOW_SEARCH_ATTRIBUTES) return true;
+  return false;
+}
+
+// RequestId of event number `target` of the task at exec slot `slot`, counted across the workflow's blobs: 0x59,
+// shared.History{10 list<HistoryEvent{30 eventType, 90 decisionTaskStartedEventAttributes{30 requestId}}>}.  false:
+// no blobs, the event is not there, it is not a DecisionTaskStarted, or a blob is malformed.  The string lies within
+// the batch's bytes.
+CRR_HD bool exec_request_id(const ExecIn& x, uint64_t slot, int64_t target, uint64_t& off, uint32_t& len, Frame* stk) {
+  off = 0, len = 0;
+  if (!x.tb_bytes || !x.tb_off || !x.tb_wf || slot >= x.tb_n_wf || target < 0) return false;
+  const crr_blob_wf W = x.tb_wf[slot];
+  if ((uint64_t)W.blob_begin + W.blob_count > x.tb_n_blobs) return false;
+  const uint64_t total = x.tb_off[x.tb_n_blobs];
+  for (uint32_t b = W.blob_begin; b < W.blob_begin + W.blob_count; ++b) {
+    Rd r = {x.tb_bytes, x.tb_off[b], x.tb_off[b + 1], false};
+    if (r.end < r.pos || r.end > total) return false;
+    if (r.end == r.pos) continue;   // an empty batch is an empty blob
+    if (rd_u8(r) != 0x59) return false;
+    uint8_t t, t2, t3;
+    int16_t id, id2, id3;
+    while (next_field(r, t, id)) {
+      if (id != 10 || t != T_LIST) {
+        skip(r, t, stk);
+        continue;
+      }
+      const uint8_t et = rd_u8(r);
+      const int32_t n = rd_i32(r);
+      if (r.bad || et != T_STRUCT || n < 0 || (uint64_t)n > r.end - r.pos) return false;
+      const int64_t before = target < n ? target : n;
+      for (int64_t k = 0; k < before; ++k) skip(r, T_STRUCT, stk);
+      if (r.bad) return false;
+      target -= before;
+      if (before == n) continue;
+      int32_t etype = -1;
+      bool attrs = false;
+      while (next_field(r, t2, id2)) {
+        if (id2 == 30 && t2 == T_I32) {
+          etype = rd_i32(r);
+        } else if (id2 == 90 && t2 == T_STRUCT) {
+          attrs = true;
+          while (next_field(r, t3, id3)) {
+            if (id3 == 30 && t3 == T_STRING) rd_str(r, off, len);
+            else skip(r, t3, stk);
+          }
+        } else {
+          skip(r, t2, stk);
+        }
+      }
+      return !r.bad && etype == CRR_EV_DECISION_TASK_STARTED && attrs;
+    }
+    if (r.bad) return false;
+  }
+  return false;
+}
+
+// the stored blob's top-level fields once: which overridden fields it holds, HistorySize as stored.  false: an
+// overridden field of another thrift type or held twice (or bytes the loader did not validate)
+CRR_HD bool exec_scan(const Ctx& c, uint32_t blob, uint32_t active, uint32_t& seen, int64_t& hist, Frame* stk) {
+  Rd r = c.blob(blob);
+  seen = 0, hist = 0;
+  uint8_t t;
+  int16_t id;
+  while (next_field(r, t, id)) {
+    const int s = exec_slot_of(id);
+    if (s >= 0 && ((active >> s) & 1u)) {
+      if (t != exec_type_of(s) || ((seen >> s) & 1u)) return false;
+      seen |= 1u << s;
+      if (s == kExecSlot108) {
+        hist = rd_i64(r);
+        continue;
+      }
+    }
+    skip(r, t, stk);
+  }
+  return !r.bad;
+}
+
+// The decision for task idx: the row (outcome and status of store_task, the host flags, next_event_id; len is the
+// caller's) and, when true is returned, what the walk needs.  vh_bad: the VersionHistories plan's row disagrees.
+template <class After>
+CRR_HD bool exec_plan_task(const Ctx& c, const StoreIn& a, const After& after, const ExecIn& x, uint32_t idx,
+                           crr_exec_blob_row& row, StoreDecision& D, ExecTask& T, bool& vh_bad, Frame* stk) {
+  int32_t outcome, status;
+  mutation_decide(c, a, after, idx, D, outcome, status);
+  row.outcome = outcome, row.status = status, row.flags = 0, row.len = 0, row.next_event_id = 0;
+  const bool gen = outcome == CRR_STORE_APPLIED || outcome == CRR_STORE_BACKFILLED;
+  const crr_vh_blob_row vr = x.vh_rows[idx];
+  const uint64_t o0 = x.vh_off[idx], o1 = x.vh_off[idx + 1];
+  vh_bad = vr.outcome != outcome || o1 < o0 || o1 > x.vh_total || o1 - o0 != vr.len || gen != (vr.len != 0);
+  if (!gen || vh_bad) return false;
+  const bool apply = outcome == CRR_STORE_APPLIED;
+  const crr_exec_row& R = D.S.R;
+  row.next_event_id = R.next_event_id;   // (the backfill's view is the loaded state: the stored column)
+  const crr_state_wf W = c.in.wf[D.w];
+  uint32_t flags = 0;
+  T.active = apply ? kExecApplied : kExecBackfill;
+  T.omit18 = false;
+  T.rq_mode = 1, T.rq_off = 0, T.rq_len = 0;
+  T.now = x.xt[idx].now_ns;
+  T.vh_off = o0, T.vh_len = vr.len;
+  T.exec_blob = W.blob_begin + (uint32_t)c.aux()[D.w].exec_idx;
+  if (apply) {
+    if (mut_reset_points_differ(scratch_view(c, D.w), D.S)) flags |= CRR_EXEC_BLOB_HOST_RESET_POINTS;
+    if (exec_has_upsert(x, D.S.exec_slot, D.w)) flags |= CRR_EXEC_BLOB_HOST_SEARCH_ATTRIBUTES;
+    T.omit18 = R.completion_event_batch_id == CRR_EMPTY_EVENT_ID;
+    const int32_t src = R.decision_request_src;
+    if (src == CRR_SRC_EMPTY_UUID) T.rq_mode = 0;
+    else if (src == CRR_SRC_NONE) T.rq_mode = 1;
+    else if (src >= 0 && (uint32_t)src < W.blob_count) T.active &= ~(1u << kExecSlot74);   // the load's: as stored
+    else if (src >= 0 && exec_request_id(x, D.S.exec_slot, (int64_t)src - (int64_t)W.blob_count, T.rq_off, T.rq_len, stk)) T.rq_mode = 2;
+    else flags |= CRR_EXEC_BLOB_HOST_REQUEST_ID;
+  }
+  int64_t stored_hist;
+  if (!exec_scan(c, T.exec_blob, T.active, T.seen, stored_hist, stk)) flags |= CRR_EXEC_BLOB_HOST_STORED_SHAPE;
+  T.hist = (int64_t)((uint64_t)stored_hist + (uint64_t)x.xt[idx].history_size_delta);
+  row.flags = flags;
+  return flags == 0;
+}
+
+// the emitter that records the edit script: neighbouring copies from one source merge, so a blob Go wrote takes a
+// dozen segments; `overflow`: more edits than a script holds, or a blob past 2^30 bytes
+struct ExecScriptEm {
+  ExecScript* S;
+  uint32_t n_seg, n_patch, dst;
+  bool overflow;
+  CRR_HD void seg(uint32_t kind, uint64_t src, uint32_t len) {
+    if (len == 0 || overflow) return;
+    if ((uint64_t)dst + len > kSegLenMask) {
+      overflow = true;
+      return;
+    }
+    if (kind != kSegLit && n_seg) {
+      ExecSeg& L = S->seg[n_seg - 1];
+      if ((L.len_kind >> 30) == kind && L.src + (L.len_kind & kSegLenMask) == src) {
+        L.len_kind += len;
+        dst += len;
+        return;
+      }
+    }
+    if (n_seg == (uint32_t)kExecSegs) {
+      overflow = true;
+      return;
+    }
+    const ExecSeg s = {dst, len | (kind << 30), src};
+    S->seg[n_seg++] = s;
+    dst += len;
+  }
+  CRR_HD void keep(uint64_t from, uint64_t to) { seg(kSegStored, from, (uint32_t)(to - from)); }
+  CRR_HD void patch(uint64_t at, uint32_t width, int64_t value) {
+    if (n_patch == (uint32_t)kExecPatches) overflow = true;
+    if (overflow) return;
+    const ExecPatch p = {dst, width, (uint64_t)value};
+    S->patch[n_patch++] = p;
+    seg(kSegStored, at, width);
+  }
+  CRR_HD void lit(uint64_t v, uint32_t n) { seg(kSegLit, v, n); }
+  CRR_HD void src(uint32_t kind, uint64_t off, uint32_t len) { seg(kind, off, len); }
+};
+
+// the emitter of the host restatement: the bytes themselves, in order
+struct ExecSinkEm {
+  ByteSink K;
+  const uint8_t *stored, *vh, *task;
+  CRR_HD void keep(uint64_t from, uint64_t to) {
+    for (uint64_t i = from; i < to; ++i) K.u8(stored[i]);
+  }
+  CRR_HD void patch(uint64_t, uint32_t width, int64_t value) {
+    for (uint32_t i = 0; i < width; ++i) K.u8((uint32_t)((uint64_t)value >> (8 * (width - 1 - i))));
+  }
+  CRR_HD void lit(uint64_t v, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) K.u8((uint32_t)(v >> (8 * i)));
+  }
+  CRR_HD void src(uint32_t kind, uint64_t off, uint32_t len) {
+    const uint8_t* p = kind == kSegVh ? vh : task;
+    for (uint32_t i = 0; i < len; ++i) K.u8(p[off + i]);
+  }
+};
+
+// The splice (cadence_load_store_exec.h) for a task exec_plan_task accepted.  false: the blob is not the one
+// exec_scan walked.
+template <class Em>
+CRR_HD bool exec_walk(const Ctx& c, const crr_exec_row& R, const ExecTask& T, Em& em, Frame* stk) {
+  Rd r = c.blob(T.exec_blob);
+  uint64_t cs = r.pos;                    // stored bytes [cs, cursor) are kept but not yet emitted
+  uint32_t todo = T.active & ~T.seen;     // overridden fields the stored blob lacks: to insert
+  if (T.omit18) todo &= ~(1u << kExecSlot18);
+  auto put = [&](int s) {                 // field s whole: header and new value
+    const uint32_t id = (uint32_t)exec_id_of(s);
+    const uint8_t t = exec_type_of(s);
+    const uint64_t head = t | ((uint64_t)(id >> 8) << 8) | ((uint64_t)(id & 0xffu) << 16);
+    if (t != T_STRING) {
+      const uint32_t w = exec_width_of(t);
+      const uint64_t v = (uint64_t)exec_scalar(s, R, T);
+      em.lit(head, 3);
+      em.lit(w == 8 ? __builtin_bswap64(v) : w == 4 ? (uint64_t)__builtin_bswap32((uint32_t)v) : (v & 0xffu), w);
+      return;
+    }
+    const bool uuid = s == kExecSlot74 && T.rq_mode == 0;
+    const uint32_t len = s == kExecSlot122 ? T.vh_len : s != kExecSlot74 ? 0u : uuid ? 9u : T.rq_mode == 2 ? T.rq_len : 0u;
+    em.lit(head | ((uint64_t)__builtin_bswap32(len) << 24), 7);
+    if (s == kExecSlot122) {
+      em.src(kSegVh, T.vh_off, len);
+    } else if (uuid) {
+      em.lit(0x6975557974706d65ull, 8);   // "emptyUui"
+      em.lit(0x64, 1);                    // "d"
+    } else if (len) {
+      em.src(kSegTask, T.rq_off, len);
+    }
+  };
+  auto insert_below = [&](int limit) {
+    for (int s = 0; s < kExecFields; ++s)
+      if (((todo >> s) & 1u) && exec_id_of(s) < limit) {
+        put(s);
+        todo &= ~(1u << s);
+      }
+  };
+  for (;;) {
+    const uint64_t fstart = r.pos;
+    uint8_t t;
+    int16_t id;
+    if (!next_field(r, t, id)) break;
+    if (todo) {
+      em.keep(cs, fstart);
+      cs = fstart;
+      insert_below(id);
+    }
+    const int s = exec_slot_of(id);
+    if (s < 0 || !((T.active >> s) & 1u)) {
+      skip(r, t, stk);
+      continue;
+    }
+    if (t != exec_type_of(s)) return false;
+    if (t == T_STRING) {
+      uint64_t o;
+      uint32_t l;
+      if (!rd_str(r, o, l)) return false;
+      em.keep(cs, fstart);
+      put(s);
+      cs = r.pos;
+      continue;
+    }
+    const uint32_t w = exec_width_of(t);
+    if (!need(r, w)) return false;
+    if (s == kExecSlot18 && T.omit18) {
+      em.keep(cs, fstart);
+    } else {
+      em.keep(cs, r.pos);
+      em.patch(r.pos, w, exec_scalar(s, R, T));
+    }
+    r.pos += w;
+    cs = r.pos;
+  }
+  if (r.bad) return false;
+  const uint64_t stop = r.pos - 1;        // next_field consumed the stop byte
+  em.keep(cs, stop);
+  insert_below(0x10000);
+  em.keep(stop, stop + 1);
+  return true;
+}
+
+// task idx's row, script and length (0: nothing is generated on the device)
+template <class After>
+CRR_HD uint32_t exec_size_task(const Ctx& c, const StoreIn& a, const After& after, const ExecIn& x, uint32_t idx,
+                               crr_exec_blob_row* rows, ExecScript* S, bool& vh_bad, Frame* stk) {
+  crr_exec_blob_row row;
+  StoreDecision D;
+  ExecTask T;
+  ExecScriptEm em = {S, 0, 0, 0, false};
+  uint32_t len = 0;
+  if (exec_plan_task(c, a, after, x, idx, row, D, T, vh_bad, stk)) {
+    if (exec_walk(c, D.S.R, T, em, stk) && !em.overflow) len = em.dst;
+    else row.flags |= CRR_EXEC_BLOB_HOST_STORED_SHAPE;
+  }
+  S->n_seg = len ? em.n_seg : 0;
+  S->n_patch = len ? em.n_patch : 0;
+  S->len = len;
+  S->reserved = 0;
+  row.len = len;
+  rows[idx] = row;
+  return len;
+}
+
+// The output-stationary form (load_store_exec_emit_kernel): bytes [16 * chunk, + 16) of the concatenated blobs as
+// two little-endian words.  The task is found as vh_emit_chunk finds it, the segment by walking the task's script
+// forward, then the source byte is read and a patch that covers it applied.  Counts and widths read from a script
+// are clamped to what a script holds, every source offset is checked against its buffer's size, and a script
+// whose length is not the one the offsets give is not read at all: such bytes are zero.
+struct ExecSrc {
+  const uint8_t *stored, *vh, *task;
+  uint64_t n_stored, n_vh, n_task;
+};
+CRR_HD void exec_emit_chunk(const ExecScript* scripts, const ExecSrc& q, const uint64_t* blob_off, uint32_t n_tasks,
+                            uint64_t n_bytes, uint64_t chunk, uint64_t& lo, uint64_t& hi) {
+  lo = hi = 0;
+  const uint64_t pos = chunk * 16;
+  if (pos >= n_bytes || n_tasks == 0) return;
+  uint32_t k = 0, r = n_tasks;   // the last task that starts at or before pos: blob_off[0] == 0
+  while (k + 1 < r) {
+    const uint32_t m = k + (r - k) / 2;
+    if (blob_off[m] <= pos) k = m;
+    else r = m;
+  }
+  uint64_t base = blob_off[k], end = blob_off[k + 1];
+  bool fresh = true, ok = false;
+  const ExecScript* S = scripts;
+  uint32_t n_seg = 0, n_patch = 0, j = 0, pmask = 0;
+  for (uint32_t b = 0; b < 16; ++b) {
+    const uint64_t g = pos + b;
+    if (g >= n_bytes) return;
+    while (g >= end) {   // the next task that holds bytes
+      if (++k >= n_tasks) return;
+      base = blob_off[k], end = blob_off[k + 1];
+      fresh = true;
+    }
+    if (g < base) continue;
+    if (fresh) {
+      S = scripts + k;
+      n_seg = S->n_seg < (uint32_t)kExecSegs ? S->n_seg : (uint32_t)kExecSegs;
+      n_patch = S->n_patch < (uint32_t)kExecPatches ? S->n_patch : (uint32_t)kExecPatches;
+      ok = S->len == end - base;
+      j = 0, pmask = 0;
+      const uint64_t p0 = g - base;
+      for (uint32_t i = 0; i < n_patch; ++i) {
+        const uint64_t d = S->patch[i].dst;
+        if (d < p0 + 16 && d + 8 > p0) pmask |= 1u << i;
+      }
+      fresh = false;
+    }
+    if (!ok) continue;
+    const uint32_t p = (uint32_t)(g - base);
+    while (j < n_seg && p - S->seg[j].dst >= (S->seg[j].len_kind & kSegLenMask)) ++j;
+    uint32_t v = 0;
+    if (j < n_seg) {
+      const ExecSeg sg = S->seg[j];
+      const uint64_t off = p - sg.dst;
+      const uint32_t kind = sg.len_kind >> 30;
+      if (kind == kSegLit) {
+        v = off < 8 ? (uint32_t)(sg.src >> (8 * off)) & 0xffu : 0u;
+      } else if (kind == kSegStored) {   // (a branch per source: the three buffers stay three scalars)
+        if (q.stored && sg.src < q.n_stored && off < q.n_stored - sg.src) v = q.stored[sg.src + off];
+      } else if (kind == kSegVh) {
+        if (q.vh && sg.src < q.n_vh && off < q.n_vh - sg.src) v = q.vh[sg.src + off];
+      } else {
+        if (q.task && sg.src < q.n_task && off < q.n_task - sg.src) v = q.task[sg.src + off];
+      }
+    }
+    for (uint32_t m = pmask; m; m &= m - 1) {
+      const ExecPatch P = S->patch[__builtin_ctz(m)];
+      const uint32_t w = P.width < 8 ? P.width : 8u;
+      if (p - P.dst < w) v = (uint32_t)(P.value >> (8 * (w - 1 - (p - P.dst)))) & 0xffu;
+    }
+    if (b < 8) lo |= (uint64_t)v << (8 * b);
+    else hi |= (uint64_t)v << (8 * (b - 8));
+  }
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

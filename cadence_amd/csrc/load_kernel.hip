@@ -26,6 +26,11 @@
 //                       task classifies its entries by a merge walk and counts, the block sums are scanned by
 //                       load_ndc_scan_kernel and one pass turns the counts into offsets; then one lane per task writes
 //                       the deleted keys and a directory, and one lane per 8-byte word gathers the rows through it
+//   load_store_exec_size_kernel / load_store_exec_offsets_kernel / load_store_exec_emit_kernel
+//                       the execution blob to store for the same tasks (cadence_load_store_exec.h): one lane per task
+//                       decides, walks the stored blob's top-level fields and leaves an edit script (copy segments and
+//                       scalar patches); block sums through load_ndc_scan_kernel and one pass give the offsets; then
+//                       one lane per 16 bytes of the output follows its task's script and stores them at once
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -384,6 +389,86 @@ __global__ void __launch_bounds__(kBlock) load_mutation_gather_kernel(const uint
                                                                       uint64_t n_words, uint64_t* out) {
   const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (g < n_words) out[g] = mutation_gather_word(table, dir, words, g);
+}
+
+// ---- cadence_load_store_exec.h: the execution blob to store for every routed task ------------------------------
+// The columns that are summed per block and scanned: the blobs' bytes, the tasks with a blob, the generated tasks
+// left to the host, the tasks whose VersionHistories row disagrees.
+constexpr int kExecCols = 4;
+
+// one lane per task, load_mutation_count_kernel's launch with the skip stack of the walking kernels: the decision,
+// the stored blob's top-level fields twice (which overridden fields it holds, then the splice), for a request id
+// of this task the task's events; the row, the edit script, and the block's column sums for the offsets
+__global__ void __launch_bounds__(kBlock) load_store_exec_size_kernel(Ctx c, StoreIn a, ReplayAfter after, ExecIn x,
+                                                                      crr_exec_blob_row* rows, ExecScript* scripts,
+                                                                      int64_t* block_sums, uint32_t n_blocks) {
+  __shared__ Frame stk[kBlock][kMaxDepth];
+  __shared__ unsigned long long sums[kExecCols];
+  if (threadIdx.x < kExecCols) sums[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < a.n_tasks) {
+    bool vh_bad;
+    const uint32_t len = exec_size_task(c, a, after, x, i, rows, scripts + i, vh_bad, stk[threadIdx.x]);
+    const crr_exec_blob_row o = rows[i];
+    if (len) {
+      atomicAdd(&sums[0], (unsigned long long)len);
+      atomicAdd(&sums[1], 1ull);
+    } else if (o.flags) {
+      atomicAdd(&sums[2], 1ull);
+    }
+    if (vh_bad) atomicAdd(&sums[3], 1ull);
+  }
+  __syncthreads();
+  if (threadIdx.x < kExecCols) block_sums[(uint64_t)threadIdx.x * ((uint64_t)n_blocks + 1) + blockIdx.x] = (int64_t)sums[threadIdx.x];
+}
+
+// load_mutation_offsets_kernel's scheme for the one column that becomes offsets: block_base is the scanned block
+// sums; within the block a wavefront scan of the lengths, the first wavefront's total handed over in LDS
+__global__ void __launch_bounds__(kBlock) load_store_exec_offsets_kernel(const crr_exec_blob_row* rows, uint32_t n_tasks,
+                                                                         const int64_t* block_base, uint64_t* blob_off) {
+  static_assert(kBlock == 128, "two wavefronts of 64");
+  __shared__ unsigned long long first_wave;
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool have = i < n_tasks;
+  const unsigned long long v = have ? rows[i].len : 0u;
+  unsigned long long incl = v;
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const unsigned long long o = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += o;
+  }
+  if (threadIdx.x == 63) first_wave = incl;
+  __syncthreads();
+  if (!have) return;
+  unsigned long long excl = incl - v + (unsigned long long)block_base[blockIdx.x];
+  if (threadIdx.x >= 64) excl += first_wave;
+  blob_off[i] = excl;
+  if (i + 1 == n_tasks) blob_off[n_tasks] = excl + v;
+}
+
+// output-stationary, load_store_vh_emit_kernel's shape: lane i owns bytes [16 i, 16 i + 16) of `out` and stores them
+// as one dwordx4; the lane that owns the tail past the last whole 16 stores its n_bytes - 16 i bytes one by one.
+// Which bytes a lane writes follows from its index and n_bytes alone.
+__global__ void __launch_bounds__(kBlock) load_store_exec_emit_kernel(const ExecScript* scripts, const uint8_t* stored,
+                                                                      const uint64_t* stored_off, uint32_t n_stored_blobs,
+                                                                      const uint8_t* vh, uint64_t n_vh, const uint8_t* task,
+                                                                      const uint64_t* task_off, uint32_t n_task_blobs,
+                                                                      const uint64_t* blob_off, uint32_t n_tasks,
+                                                                      uint64_t n_bytes, uint64_t n_chunks, uint8_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_chunks) return;
+  const uint64_t n_stored = stored_off ? stored_off[n_stored_blobs] : 0, n_task = task_off ? task_off[n_task_blobs] : 0;
+  const ExecSrc q = {stored, vh, task, n_stored, n_vh, n_task};
+  uint64_t lo, hi;
+  exec_emit_chunk(scripts, q, blob_off, n_tasks, n_bytes, i, lo, hi);
+  if (16 * i + 16 <= n_bytes) {
+    reinterpret_cast<ulonglong2*>(out)[i] = make_ulonglong2(lo, hi);
+  } else {
+    const uint32_t n = (uint32_t)(n_bytes - 16 * i);
+    for (uint32_t b = 0; b < n; ++b) out[16 * i + b] = (uint8_t)((b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8))) & 0xffu);
+  }
 }
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
@@ -951,6 +1036,151 @@ int crr_load_mutation_run(const crr_state_batch* in, const void* scratch, size_t
   };
   gather(replay_out->exec, d.dir_exec, sizeof(crr_exec_row), P.n_exec, out->exec);
   for (int t = 0; t < CRR_MUTATION_MAPS; ++t) gather(tables[t], d.dir[t], kRowBytes[t], P.n_upsert[t], out->upsert[t]);
+  return (int)hipGetLastError();
+}
+
+// ---- cadence_load_store_exec.h --------------------------------------------------------------------------------
+// the work buffer: the block sums [kExecCols][n_blocks + 1] (scanned in place), the totals, then a script per task
+struct ExecLayout {
+  uint64_t sums, totals, scripts, end;
+  uint32_t n_blocks;
+};
+static ExecLayout carve_exec(uint32_t n_tasks) {
+  ExecLayout L;
+  L.n_blocks = (uint32_t)(((uint64_t)n_tasks + kBlock - 1) / kBlock);
+  uint64_t o = 0;
+  L.sums = o;     o = align16(o + (uint64_t)kExecCols * ((uint64_t)L.n_blocks + 1) * sizeof(int64_t));
+  L.totals = o;   o = align16(o + kExecCols * sizeof(uint64_t));
+  L.scripts = o;  o = align16(o + (uint64_t)n_tasks * sizeof(ExecScript));
+  L.end = o;
+  return L;
+}
+
+size_t crr_load_store_exec_scratch_bytes(uint32_t n_tasks) { return (size_t)carve_exec(n_tasks).end; }
+
+// the arguments the two calls share beside store_setup's, checked and packed: 0, or -1
+static int exec_setup(uint32_t n_tasks, const crr_inputs* replay_in, const crr_exec_blob_task* exec_tasks,
+                      const crr_vh_blob_row* vh_rows, const uint64_t* vh_off, const crr_vh_blob_sizes* vh_plan_host,
+                      const crr_blob_batch* task_blobs, ExecIn& x) {
+  memset(&x, 0, sizeof x);
+  if (!vh_plan_host || vh_plan_host->err != 0 || vh_plan_host->n_tasks != n_tasks) return -1;
+  if (n_tasks && (!exec_tasks || !vh_rows || !vh_off || ((uintptr_t)vh_off & 7u))) return -1;
+  x.xt = exec_tasks;
+  x.vh_rows = vh_rows;
+  x.vh_off = vh_off;
+  x.vh_total = vh_plan_host->n_bytes;
+  if (task_blobs) {
+    const crr_blob_batch& B = *task_blobs;
+    if (B.n_wf && !B.wf) return -1;
+    if (B.n_blobs && (!B.bytes || !B.blob_off)) return -1;
+    if (B.n_wf && B.blob_off) {   // (a batch without offsets has no total to check against: it reads as absent)
+      x.tb_bytes = B.bytes;
+      x.tb_off = B.blob_off;
+      x.tb_wf = B.wf;
+      x.tb_n_blobs = B.n_blobs;
+      x.tb_n_wf = B.n_wf;
+    }
+  }
+  if (replay_in) {
+    x.etype = replay_in->ev.etype;
+    x.ev_wf = replay_in->wf;
+    x.ev_n_wf = replay_in->n_wf;
+    x.ev_stride = replay_in->stride;
+    x.ev_wave_begin = (replay_in->flags & CRR_IN_WAVE_TAIL) ? replay_in->wave_begin : replay_in->n_wf;
+  }
+  return 0;
+}
+
+int crr_load_store_exec_plan(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                             const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                             const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                             const crr_ndc_route* routes, const crr_load_branches* branches,
+                             const crr_load_ndc_sizes* ndc_plan_host, const crr_inputs* replay_in,
+                             const crr_outputs* replay_out, const uint32_t* position,
+                             const crr_exec_blob_task* exec_tasks, const crr_vh_blob_row* vh_rows,
+                             const uint64_t* vh_off, const crr_vh_blob_sizes* vh_plan_host,
+                             const crr_blob_batch* task_blobs, crr_exec_blob_row* rows, uint64_t* blob_off, void* work,
+                             size_t work_bytes, crr_exec_blob_sizes* plan, void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  ExecIn x;
+  if (!plan || store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                           ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (exec_setup(n_tasks, replay_in, exec_tasks, vh_rows, vh_off, vh_plan_host, task_blobs, x) != 0) return -1;
+  if (n_tasks && (!rows || !blob_off || !work || ((uintptr_t)work & 15u) || ((uintptr_t)blob_off & 7u) || ((uintptr_t)rows & 7u)))
+    return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  const ExecLayout L = carve_exec(n_tasks);
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  plan->work_needed = plan->run_work_needed = L.end;
+  hipError_t e;
+  if (n_tasks == 0) {
+    if (blob_off && (e = hipMemsetAsync(blob_off, 0, sizeof(uint64_t), s)) != hipSuccess) return (int)e;
+    return 0;
+  }
+  if (L.end > work_bytes) {
+    plan->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    return 0;
+  }
+  uint8_t* w = static_cast<uint8_t*>(work);
+  int64_t* sums = reinterpret_cast<int64_t*>(w + L.sums);
+  uint64_t* totals = reinterpret_cast<uint64_t*>(w + L.totals);
+  ExecScript* scripts = reinterpret_cast<ExecScript*>(w + L.scripts);
+  hipLaunchKernelGGL(load_store_exec_size_kernel, dim3(L.n_blocks), dim3(kBlock), 0, s, c, a, after, x, rows, scripts, sums,
+                     L.n_blocks);
+  hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, sums, L.n_blocks, kExecCols, totals);
+  hipLaunchKernelGGL(load_store_exec_offsets_kernel, dim3(L.n_blocks), dim3(kBlock), 0, s, rows, n_tasks, sums, blob_off);
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[kExecCols];
+  if ((e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  plan->n_bytes = h[0];
+  plan->n_blobs = h[1];
+  plan->n_host = h[2];
+  return h[3] ? -1 : 0;
+}
+
+int crr_load_store_exec_run(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                            const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                            const crr_last_event* last_events, const crr_ndc_result* results, const crr_ndc_route* routes,
+                            const crr_load_branches* branches, const crr_load_ndc_sizes* ndc_plan_host,
+                            const crr_inputs* replay_in, const crr_outputs* replay_out, const uint32_t* position,
+                            const crr_exec_blob_task* exec_tasks, const crr_vh_blob_row* vh_rows, const uint64_t* vh_off,
+                            const crr_vh_blob_sizes* vh_plan_host, const crr_blob_batch* task_blobs,
+                            const crr_exec_blob_row* rows, const uint64_t* blob_off, const void* work, size_t work_bytes,
+                            const crr_exec_blob_sizes* plan_host, const uint8_t* vh_bytes, uint8_t* out_bytes,
+                            size_t out_capacity, void* stream) {
+  Ctx c;
+  StoreIn a;
+  ReplayAfter after;
+  ExecIn x;
+  if (!plan_host || plan_host->err != 0) return -1;
+  const uint32_t n_tasks = plan_host->n_tasks;
+  if (store_setup(in, scratch, scratch_bytes, summary_host, tasks, last_events, n_tasks, results, routes, branches,
+                  ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
+    return -1;
+  if (exec_setup(n_tasks, replay_in, exec_tasks, vh_rows, vh_off, vh_plan_host, task_blobs, x) != 0) return -1;
+  const ExecLayout L = carve_exec(n_tasks);
+  if (n_tasks && (!rows || !blob_off || !work || ((uintptr_t)work & 15u) || L.end > work_bytes)) return -1;
+  const uint64_t n_bytes = plan_host->n_bytes;
+  if ((n_tasks == 0 && n_bytes != 0) || (uint64_t)out_capacity < n_bytes) return -1;
+  if (n_bytes && (!out_bytes || ((uintptr_t)out_bytes & 15u))) return -1;
+  if (x.vh_total && !vh_bytes) return -1;
+  const uint64_t n_chunks = (n_bytes + 15) / 16, blocks = (n_chunks + kBlock - 1) / kBlock;
+  if (n_chunks < n_bytes / 16 || blocks > 0x7FFFFFFFull) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_chunks == 0) return 0;
+  const ExecScript* scripts = reinterpret_cast<const ExecScript*>(static_cast<const uint8_t*>(work) + L.scripts);
+  hipLaunchKernelGGL(load_store_exec_emit_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, scripts, in->bytes,
+                     in->n_blobs ? in->blob_off : nullptr, in->n_blobs, vh_bytes, x.vh_total, x.tb_bytes, x.tb_off,
+                     x.tb_n_blobs, blob_off, n_tasks, n_bytes, n_chunks, out_bytes);
   return (int)hipGetLastError();
 }
 

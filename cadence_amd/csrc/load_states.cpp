@@ -6,7 +6,8 @@
 // crr_load_branches_host (include/cadence_load_ndc.h) the same load, then its branch walk;
 // crr_load_store_checksums_host (include/cadence_load_store.h) both, then load_decode.h's store_task per task;
 // crr_load_store_vh_host (include/cadence_load_store_vh.h) the same, then its sizes and its sequential blob writer;
-// crr_load_mutation_host (include/cadence_load_mutation.h) the same, then its count and emit passes and the gather.
+// crr_load_mutation_host (include/cadence_load_mutation.h) the same, then its count and emit passes and the gather;
+// crr_load_store_exec_host (include/cadence_load_store_exec.h) the same, then its decision and its splice per task.
 #include <stdlib.h>
 
 #include <thread>
@@ -390,6 +391,130 @@ extern "C" int crr_load_mutation_host(const crr_state_batch* in, const crr_repl_
   }
   for (uint64_t* p : dir) free(p);
   free(my_rows);
+  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
+  free(k.s);
+  free(c.s);
+  return ret;
+}
+
+// the execution blob to store for routed tasks (include/cadence_load_store_exec.h): the same load, branch walk and
+// decision; the VersionHistories blobs of the same tasks written first into a buffer of this call (as
+// crr_load_store_vh_host writes them); then load_decode.h's decision and splice per task -- sized through the edit
+// script the device records (so both builds flag the same blobs), written by the sequential ByteSink emitter
+extern "C" int crr_load_store_exec_host(const crr_state_batch* in, const crr_repl_task* tasks,
+                                        const crr_last_event* last_events, uint32_t n_tasks, const crr_ndc_result* results,
+                                        const crr_ndc_route* routes, const crr_load_image* after,
+                                        const crr_exec_blob_task* exec_tasks, const crr_blob_batch* task_blobs,
+                                        const uint8_t* upserts, crr_exec_blob_row* rows, uint64_t* blob_off, uint8_t* out,
+                                        size_t out_capacity, crr_exec_blob_sizes* plan, int threads) {
+  if (!in || !plan || (n_tasks && (!tasks || !last_events || !results || !routes || !exec_tasks))) return -1;
+  if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
+  if (task_blobs && ((task_blobs->n_wf && !task_blobs->wf) || (task_blobs->n_blobs && (!task_blobs->bytes || !task_blobs->blob_off))))
+    return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
+  NdcWork k;
+  if (count_branches(c, threads, k) != 0) {
+    free(c.s);
+    return -2;
+  }
+  StoreIn a;
+  a.tasks = tasks;
+  a.last = last_events;
+  a.results = results;
+  a.routes = routes;
+  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
+  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
+  a.n_tasks = n_tasks;
+  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
+  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
+  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
+  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
+  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
+  crr_vh_blob_row* vh_rows = static_cast<crr_vh_blob_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_vh_blob_row)));
+  uint64_t* vh_off = static_cast<uint64_t*>(calloc((size_t)n_tasks + 1, sizeof(uint64_t)));
+  crr_exec_blob_row* my_rows = static_cast<crr_exec_blob_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_exec_blob_row)));
+  uint64_t* my_off = static_cast<uint64_t*>(calloc((size_t)n_tasks + 1, sizeof(uint64_t)));
+  uint8_t* vh_bytes = nullptr;
+  int ret = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current && vh_rows && vh_off && my_rows && my_off ? 0 : -2;
+  if (ret == 0) {
+    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
+    const ImageAfter img = {after, n_wf};
+    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { vh_off[i] = vh_size_task(c, a, img, i, vh_rows); });
+    uint64_t run = 0;
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+      const uint64_t len = vh_off[i];
+      vh_off[i] = run;
+      run += len;
+    }
+    vh_off[n_tasks] = run;
+    vh_bytes = static_cast<uint8_t*>(calloc((size_t)run + 1, 1));
+    if (!vh_bytes) ret = -2;
+  }
+  if (ret == 0) {
+    const ImageAfter img = {after, n_wf};
+    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) {
+      const uint64_t len = vh_off[i + 1] - vh_off[i];
+      if (len == 0) return;
+      StoreDecision D;
+      store_decide(c, a, img, i, D);
+      ByteSink K = {vh_bytes + vh_off[i], len, 0};
+      if (!D.generated() || !vh_blob_write(K, c, a, D) || K.len != len) memset(vh_bytes + vh_off[i], 0, (size_t)len);
+    });
+    ExecIn x;
+    memset(&x, 0, sizeof x);
+    x.xt = exec_tasks;
+    x.vh_rows = vh_rows;
+    x.vh_off = vh_off;
+    x.vh_total = vh_off[n_tasks];
+    if (task_blobs && task_blobs->n_wf && task_blobs->blob_off) {
+      x.tb_bytes = task_blobs->bytes;
+      x.tb_off = task_blobs->blob_off;
+      x.tb_wf = task_blobs->wf;
+      x.tb_n_blobs = task_blobs->n_blobs;
+      x.tb_n_wf = task_blobs->n_wf;
+    }
+    x.upserts = upserts;
+    parallel_for(n_tasks, threads, [&](uint32_t i, Frame* stk) {
+      ExecScript S;
+      bool vh_bad;
+      my_off[i] = exec_size_task(c, a, img, x, i, my_rows, &S, vh_bad, stk);
+    });
+    memset(plan, 0, sizeof *plan);
+    plan->n_tasks = n_tasks;
+    uint64_t run = 0;
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+      const uint64_t len = my_off[i];
+      my_off[i] = run;
+      run += len;
+      plan->n_blobs += len != 0;
+      plan->n_host += len == 0 && my_rows[i].flags != 0;
+    }
+    my_off[n_tasks] = run;
+    plan->n_bytes = run;
+    if (out && (uint64_t)out_capacity < run) {
+      ret = -1;   // nothing written
+    } else {
+      if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_exec_blob_row));
+      if (blob_off) memcpy(blob_off, my_off, ((size_t)n_tasks + 1) * sizeof(uint64_t));
+      if (out) {
+        parallel_for(n_tasks, threads, [&](uint32_t i, Frame* stk) {
+          const uint64_t len = my_off[i + 1] - my_off[i];
+          if (len == 0) return;
+          crr_exec_blob_row row;
+          StoreDecision D;
+          ExecTask T;
+          bool vh_bad;
+          ExecSinkEm em = {{out + my_off[i], len, 0}, in->bytes, vh_bytes, x.tb_bytes};
+          if (!exec_plan_task(c, a, img, x, i, row, D, T, vh_bad, stk) || !exec_walk(c, D.S.R, T, em, stk) || em.K.len != len)
+            memset(out + my_off[i], 0, (size_t)len);
+        });
+      }
+    }
+  }
+  free(vh_bytes), free(vh_rows), free(vh_off), free(my_rows), free(my_off);
   free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
   free(k.s);
   free(c.s);

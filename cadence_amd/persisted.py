@@ -475,6 +475,8 @@ def _host_lib():
         L.crr_load_store_vh_host.restype = ctypes.c_int
         L.crr_load_mutation_host.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, ctypes.c_int]
         L.crr_load_mutation_host.restype = ctypes.c_int
+        L.crr_load_store_exec_host.argtypes = [vp, vp, vp, ctypes.c_uint32] + [vp] * 9 + [ctypes.c_size_t, vp, ctypes.c_int]
+        L.crr_load_store_exec_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -737,6 +739,62 @@ def mutation_host(sbs: StateBlobSet, tasks, last_events, results, routes, after:
     return Mutation(rows, ex, up, de)
 
 
+# ---- the execution blob to store with them (include/cadence_load_store_exec.h) -----------------------------------
+def exec_blob_tasks(now_ns, history_size_delta) -> np.ndarray:
+    """``abi.EXEC_BLOB_TASK`` rows from the tasks' commit clocks and history-size deltas."""
+    out = np.zeros(len(now_ns), abi.EXEC_BLOB_TASK)
+    out["now_ns"], out["history_size_delta"] = now_ns, history_size_delta
+    return out
+
+
+def _c_task_blobs(bs, ptr):
+    """``crr_blob_batch`` over a ``blobs.BlobSet`` of the tasks' event blobs (only the fields the encoder reads)."""
+    from .ingest import CBlobBatch
+    c = CBlobBatch()
+    c.bytes, c.blob_off, c.wf = ptr(bs.bytes), ptr(bs.blob_off), ptr(bs.wf)
+    c.n_blobs, c.n_wf = bs.n_blobs, bs.n_wf
+    return c
+
+
+def store_executions_host(sbs: StateBlobSet, tasks, last_events, results, routes, exec_tasks,
+                          after: Optional[LoadedStates] = None, task_blobs=None, upserts=None, threads: int = 1):
+    """The execution blob to store with each task's state once the task is committed, by the host restatement
+    (``crr_load_store_exec_host``), arguments as ``store_checksums_host`` and: ``exec_tasks`` ``abi.EXEC_BLOB_TASK``
+    per task; ``task_blobs`` a ``blobs.BlobSet`` of the tasks' event blobs, workflow w of it the task of workflow w
+    (None: a request id of the task leaves the blob to the host); ``upserts`` per workflow whether the task's events
+    hold an UpsertWorkflowSearchAttributes.  ``(rows abi.EXEC_BLOB_ROW[n], blob_off uint64[n + 1], bytes uint8[])``
+    -- task k's blob is ``bytes[blob_off[k]:blob_off[k + 1]]``, empty unless the device encodes it."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
+    xt = np.ascontiguousarray(exec_tasks, dtype=abi.EXEC_BLOB_TASK)
+    n = int(tasks.shape[0])
+    if xt.shape != (n,):
+        raise ValueError(f"{xt.shape} exec_tasks rows for {n} tasks")
+    img, _keep = _after_image(after, sbs.n_wf)
+    tb = _c_task_blobs(task_blobs, lambda a: a.ctypes.data if a.size else None) if task_blobs is not None else None
+    up = None if upserts is None else np.ascontiguousarray(upserts, dtype=np.uint8)
+    if up is not None and up.shape != (sbs.n_wf,):
+        raise ValueError(f"{up.shape} upsert flags for {sbs.n_wf} workflows")
+    P = abi.CExecBlobSizes()
+
+    def ptr(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    def call(rows, off, out):
+        rc = L.crr_load_store_exec_host(ctypes.byref(c), ptr(tasks), ptr(last), n, ptr(results), ptr(routes),
+                                        ctypes.byref(img) if img is not None else None, ptr(xt),
+                                        ctypes.byref(tb) if tb is not None else None, ptr(up), rows, off, out[0], out[1],
+                                        ctypes.byref(P), threads)
+        if rc != 0:
+            raise RuntimeError(f"crr_load_store_exec_host failed: {rc}")
+    call(None, None, (None, 0))   # sizes
+    rows, off = np.zeros(n, abi.EXEC_BLOB_ROW), np.zeros(n + 1, np.uint64)
+    out = np.zeros(max(int(P.n_bytes), 1), np.uint8)
+    call(ptr(rows), off.ctypes.data, (out.ctypes.data, int(P.n_bytes)))
+    return rows, off, out[:int(P.n_bytes)].copy()
+
+
 def _struct_fields(raw: bytes) -> Dict[int, bytes]:
     """The top-level fields of a thrift-binary struct whose fields are scalars, binaries, list<binary> or
     map<binary, binary> (the six state structs): field id -> the bytes of a binary field, b"" for any other."""
@@ -773,7 +831,8 @@ _MAP_KIND = {"act": abi.STATE_ACTIVITY, "timer": abi.STATE_TIMER, "child": abi.S
              "sig": abi.STATE_SIGNAL}
 
 
-def apply_mutation(sbs: StateBlobSet, tasks, mutation: Mutation, vh_blobs, checksums, names, reset_points=None) -> StateBlobSet:
+def apply_mutation(sbs: StateBlobSet, tasks, mutation: Mutation, vh_blobs, checksums, names, reset_points=None,
+                   exec_blobs=None) -> StateBlobSet:
     """What a host shim does with the device's result: the store after every generated task's write.  For each task
     whose outcome is ``APPLIED`` or ``BACKFILLED`` its state's blobs (other states are kept as they are): the
     entries whose keys the mutation deletes dropped, the blobs of the upserted rows replaced or added (encoded with
@@ -784,7 +843,9 @@ def apply_mutation(sbs: StateBlobSet, tasks, mutation: Mutation, vh_blobs, check
     ``{key id: string}`` or the interner ``{string: key id}``.  ``reset_points``: ``{workflow: [(binary checksum,
     resettable)]}`` for the tasks flagged ``MUTATION_RESET_POINTS_CHANGED`` (the reset-point rows are not part of
     the mutation); the others keep their stored ``AutoResetPoints``.  A state with more than one generated task takes
-    the last one's write."""
+    the last one's write.  ``exec_blobs``: ``store_executions``' ``(rows, blob_off, bytes)``; a task with a blob there
+    (``len`` > 0) takes it verbatim as its execution blob and ``next_event_id`` from its row, the others (left to the
+    host by a ``EXEC_BLOB_HOST_*`` flag) are encoded here as without it."""
     tasks = np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
     vh_rows, vh_off, vh_bytes = vh_blobs
     rows = mutation.rows
@@ -810,23 +871,36 @@ def apply_mutation(sbs: StateBlobSet, tasks, mutation: Mutation, vh_blobs, check
         blobs = states[w][1]
         vh = bytes(vh_bytes[int(vh_off[k]):int(vh_off[k + 1])])
         ei = [i for i, b in enumerate(blobs) if b[0] == abi.STATE_EXECUTION][0]
-        old = _struct_fields(blobs[ei][4])
+        ready = None                                 # the execution blob as the device wrote it
+        if exec_blobs is not None:
+            x_rows, x_off, x_bytes = exec_blobs
+            if int(x_rows[k]["outcome"]) != outcome:
+                raise ValueError(f"task {k}: the execution blobs and the mutation disagree on the outcome")
+            if int(x_rows[k]["len"]):
+                ready = bytes(x_bytes[int(x_off[k]):int(x_off[k + 1])])
+        if ready is not None:
+            blobs[ei] = (abi.STATE_EXECUTION, 0, 0, "", ready)
+            states[w][0] = int(x_rows[k]["next_event_id"])
+            if outcome == abi.StoreOutcome.BACKFILLED:
+                continue
+        old = _struct_fields(blobs[ei][4]) if ready is None else None
         if outcome == abi.StoreOutcome.BACKFILLED:   # only field 122 changes: the blob's other bytes are kept
             raw = blobs[ei][4]
             at = raw.index(struct.pack(">bhi", T_STRING, 122, len(old[122])) + old[122])
             blobs[ei] = blobs[ei][:4] + (raw[:at] + struct.pack(">bhi", T_STRING, 122, len(vh)) + vh + raw[at + 7 + len(old[122]):],)
             continue
-        ex = mutation.exec_of(k)
-        v = execution_values(ex, old[104], [], [])
-        v["VersionHistories"] = vh
-        if int(rows[k]["flags"]) & abi.MUTATION_RESET_POINTS_CHANGED:
-            if reset_points is None or w not in reset_points:
-                raise ValueError(f"task {k}: the reset points of workflow {w} changed and none were given")
-            v["AutoResetPoints"] = encode_reset_points(reset_points[w])
-        else:
-            v["AutoResetPoints"] = old[115]
-        blobs[ei] = (abi.STATE_EXECUTION, 0, 0, "", encode_struct("WorkflowExecutionInfo", v))
-        states[w][0] = int(ex["next_event_id"])
+        if ready is None:
+            ex = mutation.exec_of(k)
+            v = execution_values(ex, old[104], [], [])
+            v["VersionHistories"] = vh
+            if int(rows[k]["flags"]) & abi.MUTATION_RESET_POINTS_CHANGED:
+                if reset_points is None or w not in reset_points:
+                    raise ValueError(f"task {k}: the reset points of workflow {w} changed and none were given")
+                v["AutoResetPoints"] = encode_reset_points(reset_points[w])
+            else:
+                v["AutoResetPoints"] = old[115]
+            blobs[ei] = (abi.STATE_EXECUTION, 0, 0, "", encode_struct("WorkflowExecutionInfo", v))
+            states[w][0] = int(ex["next_event_id"])
         for name in abi.MUTATION_MAPS:
             kind = _MAP_KIND[name]
 
@@ -938,6 +1012,13 @@ class StateLoader:
         L.crr_load_mutation_plan.restype = ctypes.c_int
         L.crr_load_mutation_run.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 11 + [ctypes.c_size_t, vp]
         L.crr_load_mutation_run.restype = ctypes.c_int
+        L.crr_load_store_exec_scratch_bytes.argtypes = [ctypes.c_uint32]
+        L.crr_load_store_exec_scratch_bytes.restype = ctypes.c_size_t
+        L.crr_load_store_exec_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32] + [vp] * 15 + [ctypes.c_size_t, vp, vp]
+        L.crr_load_store_exec_plan.restype = ctypes.c_int
+        L.crr_load_store_exec_run.argtypes = ([vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 15 +
+                                              [ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp])
+        L.crr_load_store_exec_run.restype = ctypes.c_int
         self.last_ndc = None
         self.scratch = None
         self.scratch_bytes = 0
@@ -1269,6 +1350,93 @@ class StateLoader:
             return plan.tensors["rows"], out, plan
         m = plan.download(out)
         return m.rows, m
+
+
+    # ---- include/cadence_load_store_exec.h -----------------------------------------------------------------
+    def store_executions_plan(self, vh_plan: "VhBlobPlan", exec_tasks, task_blobs=None) -> "ExecBlobPlan":
+        """Decide, size and script (``crr_load_store_exec_plan``, one synchronisation) the execution blobs of the tasks
+        ``vh_plan`` (``store_version_histories_plan``) was made for.  ``exec_tasks``: ``abi.EXEC_BLOB_TASK`` per task;
+        ``task_blobs``: the tasks' event blobs resident in HBM (an ``ingest.DeviceBlobs``, workflow p of it device
+        position p: the batch ``crr_ingest_plan_resume`` took), None: a request id of the task leaves its blob to the
+        host.  The rows, offsets and scripts stay on the device; ``plan.sizes.n_bytes`` is what the run writes."""
+        from .engine import _dev_bytes
+        torch, dev, n = self.torch, self.engine.dev, vh_plan.n
+        xt = np.ascontiguousarray(exec_tasks, dtype=abi.EXEC_BLOB_TASK)
+        if xt.shape != (n,):
+            raise ValueError(f"{xt.shape} exec_tasks rows for {n} tasks")
+        work_bytes = int(self.lib.crr_load_store_exec_scratch_bytes(n))
+        T = {"exec_tasks": _dev_bytes(torch, xt, dev), "task_blobs": task_blobs,
+             "rows": torch.empty(max(n, 1) * abi.EXEC_BLOB_ROW.itemsize, dtype=torch.uint8, device=dev),
+             "blob_off": torch.empty((n + 1) * 8, dtype=torch.uint8, device=dev),
+             "work": torch.empty(work_bytes + 16, dtype=torch.uint8, device=dev)}
+        V = vh_plan.tensors
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+        mid = (ptr(T["exec_tasks"]), ptr(V["rows"]), ptr(V["blob_off"]), ctypes.byref(vh_plan.sizes),
+               ctypes.byref(task_blobs.c) if task_blobs is not None else None)
+        P = abi.CExecBlobSizes()
+        rc = self.lib.crr_load_store_exec_plan(*vh_plan.head, n, *vh_plan.tail, *mid, ptr(T["rows"]), ptr(T["blob_off"]),
+                                               ptr(T["work"]), ctypes.c_size_t(work_bytes), ctypes.byref(P), self._stream())
+        if rc != 0 or P.err != 0:
+            raise RuntimeError(f"crr_load_store_exec_plan failed: {rc} (err {P.err})")
+        return ExecBlobPlan(n, P, T, vh_plan, mid, work_bytes)
+
+    def store_executions_run(self, plan: "ExecBlobPlan", vh_bytes, out=None, capacity: Optional[int] = None):
+        """Emit the planned blobs (``crr_load_store_exec_run``, enqueued on the current stream behind the
+        ``store_version_histories_run`` that wrote ``vh_bytes``) into ``out``, a device uint8 tensor whose start is
+        16-byte aligned (default: one of exactly ``n_bytes``), of which ``capacity`` bytes (default: all) may be
+        written; returns ``out``.  Too small a capacity raises and launches nothing."""
+        n_bytes = int(plan.sizes.n_bytes)
+        if out is None:
+            out = self.torch.empty(max(n_bytes, 16), dtype=self.torch.uint8, device=self.engine.dev)
+        capacity = int(out.numel() if capacity is None else capacity)
+        T, v = plan.tensors, plan.vh_plan
+
+        def ptr(t):
+            return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+        rc = self.lib.crr_load_store_exec_run(*v.head, *v.tail, *plan.mid, ptr(T["rows"]), ptr(T["blob_off"]), ptr(T["work"]),
+                                              ctypes.c_size_t(plan.work_bytes), ctypes.byref(plan.sizes), ptr(vh_bytes),
+                                              ptr(out), ctypes.c_size_t(capacity), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_store_exec_run failed: {rc}")
+        T["out"], T["vh_bytes"] = out, vh_bytes
+        self.last_store_exec = plan   # alive until the stream has run the kernel
+        return out
+
+    def store_executions(self, ds: DeviceStates, tasks, last_events, exec_tasks, db=None, perm=None, task_blobs=None,
+                         on_device: bool = False):
+        """The execution blob to store with each task's state once the task is committed
+        (include/cadence_load_store_exec.h), generated on the device behind the ``VersionHistories`` blobs of the same
+        tasks; arguments as ``store_version_histories`` and ``store_executions_plan``.  Returns ``((rows
+        abi.EXEC_BLOB_ROW[n], blob_off uint64[n + 1], bytes uint8[blob_off[n]]), store_version_histories' three)`` --
+        task k's blob is ``bytes[blob_off[k]:blob_off[k + 1]]``, empty unless the device encodes it (``rows["flags"]``
+        says why not).  ``on_device``: all six as device byte tensors, nothing more copied back."""
+        vh_plan = self.store_version_histories_plan(ds, tasks, last_events, db=db, perm=perm)
+        vh_out = self.store_version_histories_run(vh_plan)
+        plan = self.store_executions_plan(vh_plan, exec_tasks, task_blobs=task_blobs)
+        out = self.store_executions_run(plan, vh_out)
+        T, V, n = plan.tensors, vh_plan.tensors, plan.n
+        if on_device:
+            return (T["rows"], T["blob_off"], out), (V["rows"], V["blob_off"], vh_out)
+        return ((plan.rows(), T["blob_off"].cpu().numpy().view(np.uint64).copy(), out[:int(plan.sizes.n_bytes)].cpu().numpy().copy()),
+                (V["rows"][:n * abi.VH_BLOB_ROW.itemsize].cpu().numpy().view(abi.VH_BLOB_ROW).copy(),
+                 V["blob_off"].cpu().numpy().view(np.uint64).copy(), vh_out[:int(vh_plan.sizes.n_bytes)].cpu().numpy().copy()))
+
+
+@dataclasses.dataclass
+class ExecBlobPlan:
+    """A finished ``crr_load_store_exec_plan``: the host sizes, the device rows / offsets / work buffer (the edit
+    scripts), the ``VersionHistories`` plan it was made from and the arguments ``crr_load_store_exec_run`` takes again."""
+    n: int
+    sizes: abi.CExecBlobSizes
+    tensors: Dict[str, object]
+    vh_plan: "VhBlobPlan"
+    mid: tuple
+    work_bytes: int
+
+    def rows(self) -> np.ndarray:
+        return self.tensors["rows"][:self.n * abi.EXEC_BLOB_ROW.itemsize].cpu().numpy().view(abi.EXEC_BLOB_ROW).copy()
 
 
 @dataclasses.dataclass
