@@ -21,6 +21,7 @@
 
 #include "cadence_decode.h"
 #include "cadence_ingest.h"
+#include "event_fields.h"
 
 namespace {
 
@@ -104,7 +105,7 @@ void encode_event(W& w, const Inputs& in, i64 x, u64 wf_no, const std::unordered
   const i64 ref = in.ref[x];
   const i32 aux = in.aux[x];
   char rid[36];
-  w.begin(40 + 10 * t);
+  w.begin(event_attr_field_of_type(t));
   switch (t) {
     case CRR_EV_WORKFLOW_EXECUTION_STARTED: {
       const crr_start_side& s = in.start[aux];

@@ -10,6 +10,7 @@
 // thrift binary: field header = type byte + big-endian i16 id, i32/i64 big-endian, binary = be32
 // length + bytes, list = element type + be32 count, struct = fields until a 0 byte.
 #include "cadence_decode.h"
+#include "event_fields.h"
 #include "host_flatten.h"
 #include "json_decode.h"
 
@@ -108,12 +109,9 @@ struct Reader {
   }
 };
 
-// Attribute field id (in HistoryEvent) -> event type: 40 + 10 * type for every type
-// (shared.go:42000-42460: WorkflowExecutionStarted 40 ... UpsertWorkflowSearchAttributes 450).
-inline int attr_type_of_field(int16_t id) {
-  if (id < 40 || id > 450 || id % 10) return -1;
-  return (id - 40) / 10;
-}
+// Attribute field id (in HistoryEvent) -> event type (shared.go:42000-42460: WorkflowExecutionStarted 40 ...
+// UpsertWorkflowSearchAttributes 450; ids 180..320 are not in EventType order, event_fields.h).
+inline int attr_type_of_field(int16_t id) { return event_attr_type_of_field(id); }
 
 void read_retry_policy(Reader& r, Attr& a) {  // RetryPolicy{60 ExpirationIntervalInSeconds i32}
   a.has_retry = 1;

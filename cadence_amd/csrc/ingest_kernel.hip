@@ -40,6 +40,7 @@
 
 #include "cadence_ingest.h"
 #include "cadence_decode.h"
+#include "event_fields.h"
 #include "stream_device.h"
 
 namespace crr_ingest {
@@ -445,10 +446,7 @@ __device__ __forceinline__ void attr_init(Attr& a) {
   a.expiration_ts = 0; a.prev_mode = -1; a.prev_pos = 0; a.prev_n = 0; a.prev_et = 0;
 }
 
-__device__ __forceinline__ int attr_type_of_field(i32 id) {
-  if (id < 40 || id > 450 || id % 10) return -1;
-  return (id - 40) / 10;
-}
+__device__ __forceinline__ int attr_type_of_field(i32 id) { return event_attr_type_of_field(id); }
 
 // RetryPolicy{60 ExpirationIntervalInSeconds i32} (Reader::want: a wrong-typed field 60 is skipped)
 template <bool G>

@@ -33,6 +33,7 @@
 
 #include "cadence_decode.h"
 #include "cadence_ingest.h"
+#include "event_fields.h"
 #include "stream_device.h"
 
 namespace crr_json {
@@ -707,7 +708,7 @@ struct TW {
 // the attribute struct of type t from the walk's final values (blob_encode.cpp / history_decode.cpp field ids)
 template <bool W>
 __device__ void emit_attributes(JR& r, TW<W>& w, int t, const Attr& a) {
-  w.field(T_STRUCT, 40 + 10 * t);
+  w.field(T_STRUCT, (u32)event_attr_field_of_type(t));
   switch (t) {
     case CRR_EV_WORKFLOW_EXECUTION_STARTED:
       if (!a.domain_id_set) w.strf(r, 12, a.domain, true);   // ParentWorkflowDomainID given: NOT_SET

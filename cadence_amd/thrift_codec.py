@@ -213,6 +213,19 @@ def attribute_fields(e: HistoryEvent, rng: Optional[random.Random] = None) -> Li
     return f
 
 
+# HistoryEvent's attribute field of each event type (shared.go:42000-42460): ids 40, 50, ... 450 in the order
+# of the thrift struct, which leaves the EventType order between TimerStarted (180) and
+# ExternalWorkflowExecutionCancelRequested (320)
+_ATTR_ORDER = list(range(14)) + [ET.TimerStarted, ET.TimerFired, ET.ActivityTaskCancelRequested,
+                                 ET.RequestCancelActivityTaskFailed, ET.ActivityTaskCanceled, ET.TimerCanceled,
+                                 ET.CancelTimerFailed, ET.MarkerRecorded, ET.WorkflowExecutionSignaled,
+                                 ET.WorkflowExecutionTerminated, ET.WorkflowExecutionCancelRequested,
+                                 ET.WorkflowExecutionCanceled, ET.RequestCancelExternalWorkflowExecutionInitiated,
+                                 ET.RequestCancelExternalWorkflowExecutionFailed,
+                                 ET.ExternalWorkflowExecutionCancelRequested] + list(range(29, 42))
+ATTR_FIELD = {int(t): 40 + 10 * k for k, t in enumerate(_ATTR_ORDER)}
+
+
 def encode_event(w: W, e: HistoryEvent):
     w.i64(10, e.id)
     w.i64(20, e.timestamp)
@@ -220,7 +233,7 @@ def encode_event(w: W, e: HistoryEvent):
     w.i64(35, e.version)
     w.i64(36, e.task_id)
     if 0 <= e.event_type <= 41:
-        fid = 40 + 10 * int(e.event_type)
+        fid = ATTR_FIELD[int(e.event_type)]
         w.struct_(fid, [fn for _, fn in attribute_fields(e)])
     w.b += b"\x00"
 

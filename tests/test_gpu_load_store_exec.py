@@ -112,6 +112,23 @@ def test_hand_states_equal_the_host_and_the_expectation(loader, hand):
     assert got3[2][int(got3[1][k]):int(got3[1][k + 1])].tobytes() == c.want.blobs[k]
 
 
+def test_hand_states_with_populated_task_blobs(loader, ingest, hand):
+    """The task blobs with every schema field present and the DecisionTaskStarted event more than 13 KB into the
+    task's bytes (full_event_cases.populated_task_blobs): the device reads the same request id, so rows, offsets and
+    bytes equal the hand expectation and the host restatement on the same blobs."""
+    import full_event_cases as fe
+    c, ds, db, lay, _tb = hand
+    perm = lay.perm if lay.perm is not None else np.arange(lay.n_wf)
+    pop = fe.populated_task_blobs(xc.task_blob_set([c.task_histories[int(w)] for w in perm]))
+    assert pop.n_bytes > 3 * 13 * 1024
+    got, _vh = loader.store_executions(ds, c.tasks, c.last_events, c.exec_tasks, db=db, perm=lay.perm,
+                                       task_blobs=ingest.upload(pop))
+    xc.assert_result(got, c.want, "hand states on the device, populated task blobs")
+    host = store_executions_host(c.sbs, c.tasks, c.last_events, c.results, c.routes, c.exec_tasks, c.after,
+                                 fe.populated_task_blobs(xc.task_blob_set(c.task_histories)), c.upserts)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(got, host))
+
+
 def test_capacity_one_byte_short_and_canaries(loader, hand):
     c, ds, db, lay, tb = hand
     torch, dev = loader.torch, loader.engine.dev

@@ -149,6 +149,27 @@ def test_hand_states_without_task_blobs_or_a_replay():
         assert data[int(off[k[name]]):int(off[k[name] + 1])].tobytes() == c.want.blobs[k[name]], name
 
 
+def test_hand_states_with_populated_task_blobs():
+    """The request id taken from task blobs shaped as a history service persists them (full_event_cases: every field
+    of the schema present, the task's first event padded so that the DecisionTaskStarted event lies beyond 13 KB):
+    exec_request_id skips whole populated events; rows, offsets and blobs are the hand case's expectation."""
+    import full_event_cases as fe
+    from thrift_tree import parse_blob
+    c = xc.hand_case()
+    plain = xc.task_blob_set(c.task_histories)
+    tb = fe.populated_task_blobs(plain)
+    w = c.names["rq_task"]
+    b0 = int(tb.wf["blob_begin"][w])
+    assert int(tb.wf["blob_count"][w]) == 3 and int(tb.blob_off[b0 + 2] - tb.blob_off[b0]) > 13 * 1024
+    started = fe._events_of(parse_blob(tb.blob(b0 + 2)))[2][1][1]                 # event number 3 of the task
+    assert len(next(f for f in started if f[1] == 90)[2]) == len(fe.SCHEMA["DecisionTaskStartedEventAttributes"][1])
+    assert tb.n_bytes > 4 * plain.n_bytes
+    got = store_executions_host(c.sbs, c.tasks, c.last_events, c.results, c.routes, c.exec_tasks, c.after, tb, c.upserts, 1)
+    xc.assert_result(got, c.want, "hand states, populated task blobs")
+    assert got[0][c.names["rq_task"]]["len"] > 0 and got[0][c.names["rq_not_started"]]["flags"] == F["rq"]
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(got, _host(c)))
+
+
 def test_capacity_one_byte_short_and_exact():
     c = xc.hand_case()
     host = persisted._host_lib()
