@@ -405,6 +405,37 @@ class CExecBlobSizes(ctypes.Structure):
                 ("run_work_needed", ctypes.c_uint64)]
 
 
+# ---- the resumed replay of routed tasks planned from loaded states (include/cadence_load_resume.h) ---------
+LOAD_RESUME_ROW = np.dtype([("outcome", "<i4"), ("position", "<u4")])
+RESUME_COUNT_ROWS = 10                        # CRR_RESUME_COUNT_ROWS: ev_count, empty_batch_at, the eight inserts
+RESUME_NO_TASK = -1                           # task_of[p] of a position without a task
+
+
+class ResumeOutcome(enum.IntEnum):
+    APPLIED = 0
+    SHADOWED = 1
+    NOT_ROUTED = 2
+    NOT_LOADED = 3
+
+
+class CLoadResumeSizes(ctypes.Structure):
+    _fields_ = [("err", ctypes.c_int32), ("n_tasks", ctypes.c_uint32), ("n_wf", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("n_applied", ctypes.c_uint64), ("n_blobs", ctypes.c_uint64),
+                ("blob_bytes", ctypes.c_uint64), ("n_keys", ctypes.c_uint64), ("key_bytes", ctypes.c_uint64),
+                ("token_bytes", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64), ("work_needed", ctypes.c_uint64)]
+
+
+class CLoadResumeOut(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_void_p), ("bytes_capacity", ctypes.c_uint64), ("blob_off", ctypes.c_void_p),
+                ("blob_capacity", ctypes.c_uint64), ("wf", ctypes.c_void_p), ("key_begin", ctypes.c_void_p),
+                ("key_count", ctypes.c_void_p), ("key_off", ctypes.c_void_p), ("key_len", ctypes.c_void_p),
+                ("key_capacity", ctypes.c_uint64), ("task_of", ctypes.c_void_p)]
+
+
+class CLoadResumeTotals(ctypes.Structure):
+    _fields_ = [("table_rows", ctypes.c_uint64 * 8), ("arena_bytes", ctypes.c_uint64)]
+
+
 SIZEOF_ORDER = [WORKFLOW, EXEC_ROW, ACTIVITY_ROW, TIMER_ROW, CHILD_ROW, INITIATED_ROW, VH_ITEM,
                 RESET_POINT_ROW, ACTIVITY_SIDE, START_SIDE, NDC_TASK, NDC_RESULT, TASK_ROW]
 
@@ -475,11 +506,13 @@ def check_layout(lib):
     for i, n in ((15, STATE_BLOB.itemsize), (16, STATE_WF.itemsize), (20, STORED_CHECKSUM.itemsize), (21, VERIFY_ROW.itemsize),
                  (22, REPL_TASK.itemsize), (23, BRANCH_TOKEN.itemsize), (26, NDC_ROUTE.itemsize),
                  (27, STORE_ROW.itemsize), (28, LAST_EVENT.itemsize), (30, VH_BLOB_ROW.itemsize),
-                 (33, MUTATION_ROW.itemsize), (36, EXEC_BLOB_TASK.itemsize), (37, EXEC_BLOB_ROW.itemsize)):
+                 (33, MUTATION_ROW.itemsize), (36, EXEC_BLOB_TASK.itemsize), (37, EXEC_BLOB_ROW.itemsize),
+                 (40, LOAD_RESUME_ROW.itemsize)):
         if lib.crr_sizeof(i) != n:
             raise RuntimeError(f"ABI layout mismatch for struct #{i}: C {lib.crr_sizeof(i)} vs numpy {n}")
     for i, st in ((13, CInputs), (14, COutputs), (17, CStateBatch), (18, CLoadSummary), (19, CLoadImage),
                   (24, CLoadBranches), (25, CLoadNdcSizes), (31, CVhBlobSizes), (34, CMutationSizes),
-                  (35, CMutationOut), (38, CExecBlobSizes)):
+                  (35, CMutationOut), (38, CExecBlobSizes), (41, CLoadResumeSizes), (42, CLoadResumeOut),
+                  (43, CLoadResumeTotals)):
         if lib.crr_sizeof(i) != ctypes.sizeof(st):
             raise RuntimeError(f"ABI layout mismatch for {st.__name__}: C {lib.crr_sizeof(i)} vs ctypes {ctypes.sizeof(st)}")

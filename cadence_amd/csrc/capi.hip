@@ -8,6 +8,7 @@
 #include "cadence_load.h"
 #include "cadence_load_ndc.h"
 #include "cadence_load_mutation.h"
+#include "cadence_load_resume.h"
 #include "cadence_load_store.h"
 #include "cadence_load_store_exec.h"
 #include "cadence_load_store_vh.h"
@@ -280,6 +281,10 @@ size_t crr_sizeof(int which) {
     case 36: return sizeof(crr_exec_blob_task);
     case 37: return sizeof(crr_exec_blob_row);
     case 38: return sizeof(crr_exec_blob_sizes);
+    case 40: return sizeof(crr_load_resume_row);
+    case 41: return sizeof(crr_load_resume_sizes);
+    case 42: return sizeof(crr_load_resume_out);
+    case 43: return sizeof(crr_load_resume_totals);
     default: return 0;
   }
 }

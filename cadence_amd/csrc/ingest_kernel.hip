@@ -39,6 +39,7 @@
 #include <stdint.h>
 
 #include "cadence_ingest.h"
+#include "cadence_load_resume.h"
 #include "cadence_decode.h"
 #include "event_fields.h"
 #include "stream_device.h"
@@ -2497,6 +2498,22 @@ int crr_ingest_layout_resume(const crr_blob_batch* in, const crr_ingest_resume* 
                              size_t scratch_bytes, const crr_ingest_summary* S, const crr_inputs* dst, void* stream) {
   if (!resume) return -1;
   return layout_impl(in, resume, scratch, scratch_bytes, S, dst, nullptr, stream);
+}
+
+// cadence_load_resume.h: the per-workflow pass's rows WI_COUNT .. WI_TASKS as the plan left them in the scratch, so a
+// caller that sizes a resumed replay from them does not restate the scratch layout
+int crr_ingest_resume_counts(const crr_blob_batch* in, void* scratch, size_t scratch_bytes, const int32_t** counts,
+                             uint64_t* stride) {
+  static_assert(WI_COUNT == 0 && WI_EMPTY_AT == 1 && WI_ACT == 2 && WI_TASKS == 9 && CRR_RESUME_COUNT_ROWS == WI_TASKS + 1,
+                "the rows cadence_load_resume.h names");
+  if (!valid_batch(in) || !scratch || !counts || !stride) return -1;
+  const size_t stmp = sort_tmp_bytes(in->n_wf);
+  const uint64_t max_events = max_events_of(scratch_bytes, in->n_blobs, in->n_wf, stmp);
+  if (max_events == 0) return -1;
+  const Carved c = carve(scratch, in->n_blobs, in->n_wf, max_events, stmp);
+  *counts = c.P.wf_info;
+  *stride = in->n_wf;
+  return 0;
 }
 
 }  // extern "C"

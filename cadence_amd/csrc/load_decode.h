@@ -43,6 +43,7 @@
 #include "cadence_load_mutation.h"
 #include "cadence_load_store_vh.h"
 #include "cadence_load_store_exec.h"
+#include "cadence_load_resume.h"
 #include "cadence_load_verify.h"
 
 #if defined(__HIPCC__)
@@ -2381,6 +2382,262 @@ CRR_HD void exec_emit_chunk(const ExecScript* scripts, const ExecSrc& q, const u
     if (b < 8) lo |= (uint64_t)v << (8 * b);
     else hi |= (uint64_t)v << (8 * (b - 8));
   }
+}
+
+// ---- cadence_load_resume.h: the resumed replay of routed tasks planned from the loaded states ----------------
+// The columns counted per position and scanned: positions with a task, their blobs, those blobs' bytes, the
+// applied states' dictionary entries, their string bytes, their tokens' bytes (each padded to 8).
+constexpr int kResCols = 6;
+enum { kResApplied = 0, kResBlobs, kResBlobBytes, kResKeys, kResKeyBytes, kResTokenBytes };
+constexpr int kResCaps = 8;                      // the eight slot tables of a descriptor
+constexpr uint32_t kResNoTask = 0xFFFFFFFFu;     // winner[p]: no task is applied at the position
+constexpr uint32_t kResBlock = 128;              // positions per block sum
+
+// the work buffer the three calls share: the winning task per position, the per-position counts scanned in place to
+// offsets ([col][n_wf + 1]), the block sums ([col][n_blocks + 1], scanned in place) and totals of the plan and of
+// the finalize (the capacities)
+struct ResumeLayout {
+  uint64_t winner, off, sums, totals, cap_sums, cap_totals, end;
+  uint32_t n_blocks;
+};
+inline ResumeLayout carve_resume(uint32_t n_wf) {
+  ResumeLayout L;
+  L.n_blocks = (uint32_t)(((uint64_t)n_wf + kResBlock - 1) / kResBlock);
+  uint64_t o = 0;
+  L.winner = o;      o = align16(o + (uint64_t)n_wf * sizeof(uint32_t));
+  L.off = o;         o = align16(o + (uint64_t)kResCols * ((uint64_t)n_wf + 1) * sizeof(uint64_t));
+  L.sums = o;        o = align16(o + (uint64_t)kResCols * ((uint64_t)L.n_blocks + 1) * sizeof(int64_t));
+  L.totals = o;      o = align16(o + kResCols * sizeof(uint64_t));
+  L.cap_sums = o;    o = align16(o + (uint64_t)kResCaps * ((uint64_t)L.n_blocks + 1) * sizeof(int64_t));
+  L.cap_totals = o;  o = align16(o + kResCaps * sizeof(uint64_t));
+  L.end = o;
+  return L;
+}
+struct ResumeWork {
+  uint8_t* s;
+  ResumeLayout L;
+  uint32_t n_wf;
+  CRR_HD uint32_t* winner() const { return reinterpret_cast<uint32_t*>(s + L.winner); }
+  CRR_HD uint64_t* off(int col) const { return reinterpret_cast<uint64_t*>(s + L.off) + (uint64_t)col * ((uint64_t)n_wf + 1); }
+  CRR_HD int64_t* sums() const { return reinterpret_cast<int64_t*>(s + L.sums); }
+  CRR_HD uint64_t* totals() const { return reinterpret_cast<uint64_t*>(s + L.totals); }
+  CRR_HD int64_t* cap_sums() const { return reinterpret_cast<int64_t*>(s + L.cap_sums); }
+  CRR_HD uint64_t* cap_totals() const { return reinterpret_cast<uint64_t*>(s + L.cap_totals); }
+};
+
+// the tasks, their routes and their event blobs (workflow k of the blob batch is task k)
+struct ResumeIn {
+  const crr_repl_task* tasks;
+  const crr_ndc_route* routes;
+  uint32_t n_tasks;
+  const uint8_t* tb_bytes;
+  const uint64_t* tb_off;
+  const crr_blob_wf* tb_wf;
+  uint32_t tb_n_blobs, tb_n_wf;
+};
+
+// a task before the winner is known: NOT_ROUTED, NOT_LOADED, or APPLIED for one that may be applied
+CRR_HD int32_t resume_candidate(const Ctx& c, const ResumeIn& r, uint32_t k) {
+  if (r.routes[k].route != CRR_ROUTE_APPLY_CURRENT) return CRR_RESUME_NOT_ROUTED;
+  const uint32_t w = r.tasks[k].wf;
+  if (w >= c.in.n_wf || c.status()[w] != CRR_LOAD_OK) return CRR_RESUME_NOT_LOADED;
+  return CRR_RESUME_APPLIED;
+}
+
+CRR_HD crr_load_resume_row resume_row(const Ctx& c, const ResumeIn& r, const uint32_t* winner, uint32_t k) {
+  crr_load_resume_row o;
+  o.outcome = resume_candidate(c, r, k);
+  o.position = 0xFFFFFFFFu;
+  if (o.outcome == CRR_RESUME_APPLIED) {
+    o.position = r.tasks[k].wf;
+    if (winner[o.position] != k) o.outcome = CRR_RESUME_SHADOWED;
+  }
+  return o;
+}
+
+// a task's blobs as they lie in the task batch: a range or offsets outside the batch read as no blobs
+struct ResumeSrc {
+  uint64_t blob0, n_blobs, byte0, n_bytes;
+};
+CRR_HD ResumeSrc resume_src(const ResumeIn& r, uint32_t k) {
+  ResumeSrc s = {0, 0, 0, 0};
+  if (k >= r.tb_n_wf || !r.tb_off || !r.tb_wf) return s;
+  const uint64_t b0 = r.tb_wf[k].blob_begin, n = r.tb_wf[k].blob_count;
+  if (b0 > r.tb_n_blobs || n > r.tb_n_blobs - b0) return s;
+  const uint64_t o0 = r.tb_off[b0], o1 = r.tb_off[b0 + n], total = r.tb_off[r.tb_n_blobs];
+  if (o1 < o0 || o1 > total) return s;
+  s.blob0 = b0;
+  s.n_blobs = n;
+  s.byte0 = o0;
+  s.n_bytes = o1 - o0;
+  return s;
+}
+
+// position p's counts, task k applied there (kResNoTask: none, all zero)
+CRR_HD void resume_counts(const Ctx& c, const ResumeIn& r, uint32_t k, uint32_t p, uint64_t v[kResCols]) {
+  for (int col = 0; col < kResCols; ++col) v[col] = 0;
+  if (k == kResNoTask) return;
+  const ResumeSrc s = resume_src(r, k);
+  v[kResApplied] = 1;
+  v[kResBlobs] = s.n_blobs;
+  v[kResBlobBytes] = s.n_bytes;
+  v[kResKeys] = (uint64_t)(c.cnt(CRR_LOAD_T_KEYS)[p + 1] - c.cnt(CRR_LOAD_T_KEYS)[p]);
+  v[kResKeyBytes] = (uint64_t)(c.cnt(CRR_LOAD_T_KEY_BYTES)[p + 1] - c.cnt(CRR_LOAD_T_KEY_BYTES)[p]);
+  v[kResTokenBytes] = ((uint64_t)(c.cnt(CRR_LOAD_T_TOKEN)[p + 1] - c.cnt(CRR_LOAD_T_TOKEN)[p]) + 7u) & ~7ull;
+}
+
+// the largest p in [0, n) with off[p] <= x, for off[0] <= x < off[n] (an empty position is never found)
+CRR_HD uint32_t resume_find(const uint64_t* off, uint32_t n, uint64_t x) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (off[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// the totals the gather addresses with: the plan's, as the host read them back
+struct ResumeTotals {
+  uint64_t n_blobs, blob_bytes, n_keys, key_bytes, n_bytes;
+};
+
+// bytes [16 i, 16 i + 16) of the gathered `bytes` as two little-endian words: the blobs, zeros to seed_base, the
+// dictionary strings; a byte past n_bytes, or whose source is no longer where the plan found it, is zero
+CRR_HD void resume_gather_chunk(const Ctx& c, const ResumeIn& r, const ResumeWork& k, const ResumeTotals& T, uint64_t i,
+                                uint64_t& lo, uint64_t& hi) {
+  lo = hi = 0;
+  const uint64_t seed_base = align16(T.blob_bytes);
+  const uint64_t* ob = k.off(kResBlobBytes);
+  const uint64_t* ok = k.off(kResKeyBytes);
+  uint32_t p = 0;
+  int region = -1;                 // the region p was found in
+  ResumeSrc src = {0, 0, 0, 0};
+  for (uint32_t b = 0; b < 16; ++b) {
+    const uint64_t o = 16 * i + b;
+    uint32_t v = 0;
+    if (o >= T.n_bytes) break;
+    if (o < T.blob_bytes) {
+      if (region != 0 || o >= ob[p + 1]) {
+        p = resume_find(ob, k.n_wf, o);
+        region = 0;
+        const uint32_t task = k.winner()[p];
+        src = task == kResNoTask ? ResumeSrc{0, 0, 0, 0} : resume_src(r, task);
+      }
+      const uint64_t d = o - ob[p];
+      if (d < src.n_bytes) v = r.tb_bytes[src.byte0 + d];
+    } else if (o >= seed_base) {
+      const uint64_t q = o - seed_base;
+      if (region != 1 || q >= ok[p + 1]) {
+        p = resume_find(ok, k.n_wf, q);
+        region = 1;
+      }
+      const uint64_t d = q - ok[p];
+      const int64_t k0 = c.cnt(CRR_LOAD_T_KEY_BYTES)[p], k1 = c.cnt(CRR_LOAD_T_KEY_BYTES)[p + 1];
+      if (k0 >= 0 && k1 >= k0 && d < (uint64_t)(k1 - k0)) v = c.key_bytes()[(uint64_t)k0 + d];
+    }
+    if (b < 8) lo |= (uint64_t)v << (8 * b);
+    else hi |= (uint64_t)v << (8 * (b - 8));
+  }
+}
+
+// entry j of the gathered blob_off (j == n_blobs: the end of the last blob)
+CRR_HD uint64_t resume_blob_off(const ResumeIn& r, const ResumeWork& k, const ResumeTotals& T, uint64_t j) {
+  if (j >= T.n_blobs) return T.blob_bytes;
+  const uint64_t* ob = k.off(kResBlobBytes);
+  const uint32_t p = resume_find(k.off(kResBlobs), k.n_wf, j);
+  const uint64_t jl = j - k.off(kResBlobs)[p], room = ob[p + 1] - ob[p];
+  const uint32_t task = k.winner()[p];
+  uint64_t rel = room;
+  if (task != kResNoTask) {
+    const ResumeSrc s = resume_src(r, task);
+    if (jl < s.n_blobs) {
+      const uint64_t o = r.tb_off[s.blob0 + jl];
+      rel = o < s.byte0 ? 0 : o - s.byte0;
+    }
+  }
+  return ob[p] + (rel < room ? rel : room);
+}
+
+// entry e of the gathered seeds: the loader's dictionary entry, its offset into the gathered bytes
+CRR_HD void resume_key(const Ctx& c, const ResumeWork& k, const ResumeTotals& T, uint64_t e, uint64_t& off, uint32_t& len) {
+  const uint64_t seed_base = align16(T.blob_bytes);
+  off = seed_base;
+  len = 0;
+  const uint32_t p = resume_find(k.off(kResKeys), k.n_wf, e);
+  const uint64_t j = e - k.off(kResKeys)[p];
+  const int64_t e0 = c.cnt(CRR_LOAD_T_KEYS)[p], e1 = c.cnt(CRR_LOAD_T_KEYS)[p + 1];
+  const int64_t k0 = c.cnt(CRR_LOAD_T_KEY_BYTES)[p], k1 = c.cnt(CRR_LOAD_T_KEY_BYTES)[p + 1];
+  if (e0 < 0 || e1 < e0 || j >= (uint64_t)(e1 - e0) || k0 < 0 || k1 < k0) return;
+  const uint64_t so = c.key_off()[(uint64_t)e0 + j], sl = c.key_len()[(uint64_t)e0 + j];
+  const uint64_t room = k.off(kResKeyBytes)[p + 1] - k.off(kResKeyBytes)[p];
+  if (so < (uint64_t)k0 || so - (uint64_t)k0 + sl > (uint64_t)(k1 - k0) || so - (uint64_t)k0 + sl > room) return;
+  off = seed_base + k.off(kResKeyBytes)[p] + (so - (uint64_t)k0);
+  len = (uint32_t)sl;
+}
+
+// position p of the gathered batch: the winning task's crr_blob_wf with its blob range rewritten
+CRR_HD crr_blob_wf resume_blob_wf(const ResumeIn& r, const ResumeWork& k, uint32_t p) {
+  crr_blob_wf o;
+  memset(&o, 0, sizeof o);
+  const uint32_t task = k.winner()[p];
+  if (task != kResNoTask && task < r.tb_n_wf && r.tb_wf) o = r.tb_wf[task];
+  else o.final_token_len = 0xFFFFFFFFu;
+  const int32_t nr = (task != kResNoTask && task < r.tb_n_wf && r.tb_wf) ? o.new_run_wf : -1;
+  o.new_run_wf = -1;
+  // (only a task that may be applied bids, so winning its workflow says it is applied)
+  if (nr >= 0 && (uint32_t)nr < r.n_tasks && r.tasks[nr].wf < k.n_wf && k.winner()[r.tasks[nr].wf] == (uint32_t)nr)
+    o.new_run_wf = (int32_t)r.tasks[nr].wf;
+  o.blob_begin = (uint32_t)k.off(kResBlobs)[p];
+  o.blob_count = (uint32_t)(k.off(kResBlobs)[p + 1] - k.off(kResBlobs)[p]);
+  return o;
+}
+
+// position p's capacities: the loaded rows (applied positions) plus this call's inserts
+CRR_HD void resume_caps(const Ctx& c, const ResumeWork& k, const int32_t* counts, uint64_t stride, uint32_t p,
+                        uint64_t cap[kResCaps]) {
+  const bool applied = k.winner()[p] != kResNoTask;
+  for (int t = 0; t < kResCaps; ++t) {
+    const int32_t ins = counts[(uint64_t)(2 + t) * stride + p];
+    const int64_t loaded = applied && t < 7 ? c.cnt(t)[p + 1] - c.cnt(t)[p] : 0;
+    const uint64_t v = (uint64_t)(loaded > 0 ? loaded : 0) + (uint64_t)(ins > 0 ? ins : 0);
+    cap[t] = v < 0x7FFFFFFFull ? v : 0x7FFFFFFFull;
+  }
+}
+
+// position p's descriptor from its capacities and their exclusive prefixes; the loaded token goes to the arena
+CRR_HD crr_workflow resume_descriptor(const Ctx& c, const ResumeWork& k, const crr_blob_wf* gathered_wf, const int32_t* counts,
+                                      uint64_t stride, uint32_t p, const uint64_t cap[kResCaps], const uint64_t base[kResCaps],
+                                      uint8_t* arena, uint64_t arena_capacity) {
+  crr_workflow d;
+  memset(&d, 0, sizeof d);
+  const bool applied = k.winner()[p] != kResNoTask;
+  const crr_blob_wf s = gathered_wf[p];
+  // (a position without blobs applies nothing, whatever the counts' source says of a workflow without batches)
+  d.ev_count = s.blob_count ? counts[p] : 0;
+  d.empty_batch_at = s.blob_count ? counts[stride + p] : -1;
+  d.init_version = s.init_version;
+  d.now_ns = s.now_ns;
+  d.final_token_len = 0xFFFFFFFFu;
+  d.act_base = (int64_t)base[0];   d.act_cap = (int32_t)cap[0];
+  d.timer_base = (int64_t)base[1]; d.timer_cap = (int32_t)cap[1];
+  d.child_base = (int64_t)base[2]; d.child_cap = (int32_t)cap[2];
+  d.rc_base = (int64_t)base[3];    d.rc_cap = (int32_t)cap[3];
+  d.sig_base = (int64_t)base[4];   d.sig_cap = (int32_t)cap[4];
+  d.vh_base = (int64_t)base[5];    d.vh_cap = (int32_t)cap[5];
+  d.rp_base = (int64_t)base[6];    d.rp_cap = (int32_t)cap[6];
+  d.task_base = (int64_t)base[7];  d.task_cap = (int32_t)cap[7];
+  d.flags = (s.flags & (CRR_WF_FLAG_NEW_RUN | CRR_WF_FLAG_REFRESH_TASKS)) | (applied ? CRR_WF_FLAG_RESUME : 0);
+  d.retention_days = s.retention_days;
+  const uint64_t at = k.off(kResTokenBytes)[p], room = k.off(kResTokenBytes)[p + 1] - at;
+  d.start_token_off = (uint32_t)at;
+  if (applied && room && at + room <= arena_capacity) {
+    const int64_t t0 = c.cnt(CRR_LOAD_T_TOKEN)[p], t1 = c.cnt(CRR_LOAD_T_TOKEN)[p + 1];
+    const uint64_t len = t0 >= 0 && t1 >= t0 && (uint64_t)(t1 - t0) <= room ? (uint64_t)(t1 - t0) : 0;
+    const uint8_t* src = c.tokens() + (len ? (uint64_t)t0 : 0);
+    for (uint64_t q = 0; q < room; ++q) arena[at + q] = q < len ? src[q] : (uint8_t)0;
+    d.start_token_len = (uint32_t)len;
+  }
+  return d;
 }
 
 inline void fill_summary(crr_load_summary* S, const Ctx& c, const int64_t* totals /* [kCounters] */, uint64_t err_blob,

@@ -31,6 +31,14 @@
 //                       decides, walks the stored blob's top-level fields and leaves an edit script (copy segments and
 //                       scalar patches); block sums through load_ndc_scan_kernel and one pass give the offsets; then
 //                       one lane per 16 bytes of the output follows its task's script and stores them at once
+//   load_resume_bid_kernel / load_resume_rows_kernel / load_resume_count_kernel / load_resume_offsets_kernel /
+//   load_resume_index_kernel / load_resume_gather_kernel / load_resume_caps_kernel / load_resume_descriptor_kernel
+//                       the resumed replay of the same tasks planned from the loaded states (cadence_load_resume.h):
+//                       one lane per task bids for its workflow (the lowest index wins), one lane per position counts
+//                       what it contributes, block sums through load_ndc_scan_kernel and one pass give the offsets;
+//                       then the gathered batch's small arrays, and one lane per 16 bytes of its bytes; after the
+//                       ingest's plan, the capacities summed the same way and one lane per position writes its
+//                       descriptor and copies its token into the arena
 // Divergence is inherent on the skip paths (every lane walks its own blob); the lane state is the reader
 // (pointer, cursor, end) and the row being built, and the skip stack for nested containers lives in LDS.
 // A workflow is one lane whatever its size: the ordering, duplicate and MAPPED passes are quadratic in its
@@ -469,6 +477,166 @@ __global__ void __launch_bounds__(kBlock) load_store_exec_emit_kernel(const Exec
     const uint32_t n = (uint32_t)(n_bytes - 16 * i);
     for (uint32_t b = 0; b < n; ++b) out[16 * i + b] = (uint8_t)((b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8))) & 0xffu);
   }
+}
+
+// ---- cadence_load_resume.h: the resumed replay of routed tasks planned from the loaded states -------------------
+static_assert(kResBlock == kBlock, "one block sum per launch block");
+
+// an exclusive scan of N columns over the block's 128 lanes: a wavefront scan per column, the first wavefront's
+// totals handed over in LDS (load_mutation_offsets_kernel's scheme).  Every lane of the block takes part.
+template <int N>
+__device__ inline void block_exclusive_scan(const uint64_t (&v)[N], uint64_t (&excl)[N], unsigned long long* first_wave) {
+  static_assert(kBlock == 128, "two wavefronts of 64");
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (int col = 0; col < N; ++col) {
+    unsigned long long incl = v[col];
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const unsigned long long o = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += o;
+    }
+    if (threadIdx.x == 63) first_wave[col] = incl;
+    excl[col] = incl - v[col];
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64) {
+#pragma unroll
+    for (int col = 0; col < N; ++col) excl[col] += first_wave[col];
+  }
+}
+
+// one lane per task: a task that may be applied bids for its workflow with its index; the lowest wins
+__global__ void __launch_bounds__(kBlock) load_resume_bid_kernel(Ctx c, ResumeIn r, ResumeWork k) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= r.n_tasks) return;
+  if (resume_candidate(c, r, i) == CRR_RESUME_APPLIED) atomicMin(&k.winner()[r.tasks[i].wf], i);
+}
+
+// one lane per task: its row, once every bid is in
+__global__ void __launch_bounds__(kBlock) load_resume_rows_kernel(Ctx c, ResumeIn r, ResumeWork k, crr_load_resume_row* rows) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < r.n_tasks) rows[i] = resume_row(c, r, k.winner(), i);
+}
+
+// one lane per position: its counts to off(col)[p] and the block's column sums
+__global__ void __launch_bounds__(kBlock) load_resume_count_kernel(Ctx c, ResumeIn r, ResumeWork k) {
+  __shared__ unsigned long long sums[kResCols];
+  if (threadIdx.x < kResCols) sums[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p < k.n_wf) {
+    uint64_t v[kResCols];
+    resume_counts(c, r, k.winner()[p], p, v);
+#pragma unroll
+    for (int col = 0; col < kResCols; ++col) {
+      k.off(col)[p] = v[col];
+      if (v[col]) atomicAdd(&sums[col], (unsigned long long)v[col]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kResCols)
+    k.sums()[(uint64_t)threadIdx.x * ((uint64_t)k.L.n_blocks + 1) + blockIdx.x] = (int64_t)sums[threadIdx.x];
+}
+
+// one pass over the counts: the scanned block sums plus the scan within the block, in place
+__global__ void __launch_bounds__(kBlock) load_resume_offsets_kernel(ResumeWork k) {
+  __shared__ unsigned long long first_wave[kResCols];
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  const bool have = p < k.n_wf;
+  uint64_t v[kResCols], excl[kResCols];
+#pragma unroll
+  for (int col = 0; col < kResCols; ++col) v[col] = have ? k.off(col)[p] : 0;
+  block_exclusive_scan<kResCols>(v, excl, first_wave);
+  if (!have) return;
+#pragma unroll
+  for (int col = 0; col < kResCols; ++col) {
+    const uint64_t e = excl[col] + (uint64_t)k.sums()[(uint64_t)col * ((uint64_t)k.L.n_blocks + 1) + blockIdx.x];
+    k.off(col)[p] = e;
+    if (p + 1 == k.n_wf) k.off(col)[k.n_wf] = e + v[col];
+  }
+}
+
+// the gathered batch's small arrays, one lane per element of the longest: position p's crr_blob_wf, seeds' range and
+// task; blob j's offset; dictionary entry e.  Each lane's store addresses follow from its index and the plan's totals.
+__global__ void __launch_bounds__(kBlock) load_resume_index_kernel(Ctx c, ResumeIn r, ResumeWork k, ResumeTotals T,
+                                                                   crr_load_resume_out out) {
+  const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g < k.n_wf) {
+    const uint32_t p = (uint32_t)g;
+    out.wf[p] = resume_blob_wf(r, k, p);
+    out.key_begin[p] = (uint32_t)k.off(kResKeys)[p];
+    out.key_count[p] = (uint32_t)(k.off(kResKeys)[p + 1] - k.off(kResKeys)[p]);
+    const uint32_t task = k.winner()[p];
+    out.task_of[p] = task == kResNoTask ? -1 : (int32_t)task;
+  }
+  if (g <= T.n_blobs) out.blob_off[g] = resume_blob_off(r, k, T, g);
+  if (g < T.n_keys) {
+    uint64_t off;
+    uint32_t len;
+    resume_key(c, k, T, g, off, len);
+    out.key_off[g] = off;
+    out.key_len[g] = len;
+  }
+}
+
+// output-stationary, load_store_exec_emit_kernel's shape: lane i owns bytes [16 i, 16 i + 16) of `out` and stores them
+// as one dwordx4; the lane that owns the tail past the last whole 16 stores its n_bytes - 16 i bytes one by one
+__global__ void __launch_bounds__(kBlock) load_resume_gather_kernel(Ctx c, ResumeIn r, ResumeWork k, ResumeTotals T,
+                                                                    uint64_t n_chunks, uint8_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_chunks) return;
+  uint64_t lo, hi;
+  resume_gather_chunk(c, r, k, T, i, lo, hi);
+  if (16 * i + 16 <= T.n_bytes) {
+    reinterpret_cast<ulonglong2*>(out)[i] = make_ulonglong2(lo, hi);
+  } else {
+    const uint32_t n = (uint32_t)(T.n_bytes - 16 * i);
+    for (uint32_t b = 0; b < n; ++b) out[16 * i + b] = (uint8_t)((b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8))) & 0xffu);
+  }
+}
+
+// one lane per position: the block's sums of the eight capacities
+__global__ void __launch_bounds__(kBlock) load_resume_caps_kernel(Ctx c, ResumeWork k, const int32_t* counts, uint64_t stride) {
+  __shared__ unsigned long long sums[kResCaps];
+  if (threadIdx.x < kResCaps) sums[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p < k.n_wf) {
+    uint64_t cap[kResCaps];
+    resume_caps(c, k, counts, stride, p, cap);
+#pragma unroll
+    for (int t = 0; t < kResCaps; ++t)
+      if (cap[t]) atomicAdd(&sums[t], (unsigned long long)cap[t]);
+  }
+  __syncthreads();
+  if (threadIdx.x < kResCaps)
+    k.cap_sums()[(uint64_t)threadIdx.x * ((uint64_t)k.L.n_blocks + 1) + blockIdx.x] = (int64_t)sums[threadIdx.x];
+}
+
+// one lane per position: the capacities again, their prefixes, the descriptor and the token's bytes into the arena
+// (a position's arena range is the plan's, checked against the capacity before anything is stored)
+__global__ void __launch_bounds__(kBlock) load_resume_descriptor_kernel(Ctx c, ResumeWork k, const crr_blob_wf* gathered_wf,
+                                                                        const int32_t* counts, uint64_t stride, crr_workflow* wf,
+                                                                        uint8_t* arena, uint64_t arena_capacity) {
+  __shared__ unsigned long long first_wave[kResCaps];
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  const bool have = p < k.n_wf;
+  uint64_t cap[kResCaps], base[kResCaps];
+#pragma unroll
+  for (int t = 0; t < kResCaps; ++t) cap[t] = 0;
+  if (have) resume_caps(c, k, counts, stride, p, cap);
+  block_exclusive_scan<kResCaps>(cap, base, first_wave);
+  if (!have) return;
+#pragma unroll
+  for (int t = 0; t < kResCaps; ++t) base[t] += (uint64_t)k.cap_sums()[(uint64_t)t * ((uint64_t)k.L.n_blocks + 1) + blockIdx.x];
+  wf[p] = resume_descriptor(c, k, gathered_wf, counts, stride, p, cap, base, arena, arena_capacity);
+}
+
+// one lane per position: a descriptor without a task does not resume (the layout's in-place pass set the flag on all)
+__global__ void __launch_bounds__(kBlock) load_resume_settle_kernel(const int32_t* task_of, crr_workflow* wf, uint32_t n_wf) {
+  const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+  if (p < n_wf && task_of[p] < 0) wf[p].flags &= ~CRR_WF_FLAG_RESUME;
 }
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
@@ -1181,6 +1349,193 @@ int crr_load_store_exec_run(const crr_state_batch* in, const void* scratch, size
   hipLaunchKernelGGL(load_store_exec_emit_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, scripts, in->bytes,
                      in->n_blobs ? in->blob_off : nullptr, in->n_blobs, vh_bytes, x.vh_total, x.tb_bytes, x.tb_off,
                      x.tb_n_blobs, blob_off, n_tasks, n_bytes, n_chunks, out_bytes);
+  return (int)hipGetLastError();
+}
+
+// ---- cadence_load_resume.h ------------------------------------------------------------------------------------
+size_t crr_load_resume_scratch_bytes(uint32_t n_wf, uint32_t n_tasks) {
+  (void)n_tasks;   // (the work is per position: the tasks only bid for one)
+  return (size_t)carve_resume(n_wf).end;
+}
+
+// the arguments the plan and the gather share, checked and packed: 0, or -1
+static int resume_setup(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                        const crr_load_summary* summary_host, const crr_repl_task* tasks, const crr_ndc_route* routes,
+                        uint32_t n_tasks, const crr_blob_batch* task_blobs, const void* work, Ctx& c, ResumeIn& r,
+                        ResumeWork& k) {
+  if (!in || !summary_host || in->n_blobs != summary_host->n_blobs || in->n_wf != summary_host->n_wf) return -1;
+  if (in->n_wf) {
+    if (!plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
+  } else {
+    memset(&c, 0, sizeof c);   // a batch without workflows has no plan to read: every task is not loaded
+  }
+  c.in = *in;
+  memset(&r, 0, sizeof r);
+  if (n_tasks && (!tasks || !task_blobs)) return -1;   // (the plan checks its routes itself)
+  r.tasks = tasks;
+  r.routes = routes;
+  r.n_tasks = n_tasks;
+  if (task_blobs) {
+    const crr_blob_batch& B = *task_blobs;
+    if (B.n_wf && !B.wf) return -1;
+    if (!B.blob_off || (B.n_blobs && !B.bytes)) return -1;
+    r.tb_bytes = B.bytes;
+    r.tb_off = B.blob_off;
+    r.tb_wf = B.wf;
+    r.tb_n_blobs = B.n_blobs;
+    r.tb_n_wf = B.n_wf;
+  }
+  k.s = const_cast<uint8_t*>(static_cast<const uint8_t*>(work));
+  k.L = carve_resume(in->n_wf);
+  k.n_wf = in->n_wf;
+  return 0;
+}
+
+int crr_load_resume_plan(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                         const crr_load_summary* summary_host, const crr_repl_task* tasks, const crr_ndc_route* routes,
+                         uint32_t n_tasks, const crr_blob_batch* task_blobs, crr_load_resume_row* rows, void* work,
+                         size_t work_bytes, crr_load_resume_sizes* plan, void* stream) {
+  Ctx c;
+  ResumeIn r;
+  ResumeWork k;
+  if (!plan || resume_setup(in, scratch, scratch_bytes, summary_host, tasks, routes, n_tasks, task_blobs, work, c, r, k) != 0)
+    return -1;
+  if (n_tasks && (!routes || !rows || ((uintptr_t)rows & 3u))) return -1;
+  if (in->n_wf && (!work || ((uintptr_t)work & 15u))) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  plan->n_wf = in->n_wf;
+  plan->work_needed = k.L.end;
+  hipError_t e;
+  if (in->n_wf == 0) {   // no position: every task is not routed or not loaded
+    if (n_tasks) hipLaunchKernelGGL(load_resume_rows_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, r, k, rows);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    return (int)hipStreamSynchronize(s);
+  }
+  if (k.L.end > work_bytes) {
+    plan->err = CRR_INGEST_SCRATCH_TOO_SMALL;
+    return 0;
+  }
+  if ((e = hipMemsetAsync(k.winner(), 0xFF, (size_t)in->n_wf * sizeof(uint32_t), s)) != hipSuccess) return (int)e;
+  if (n_tasks) {
+    hipLaunchKernelGGL(load_resume_bid_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, r, k);
+    hipLaunchKernelGGL(load_resume_rows_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, r, k, rows);
+  }
+  hipLaunchKernelGGL(load_resume_count_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, c, r, k);
+  hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, k.sums(), k.L.n_blocks, kResCols, k.totals());
+  hipLaunchKernelGGL(load_resume_offsets_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, k);
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[kResCols];
+  if ((e = hipMemcpyAsync(h, k.totals(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  plan->n_applied = h[kResApplied];
+  plan->n_blobs = h[kResBlobs];
+  plan->blob_bytes = h[kResBlobBytes];
+  plan->n_keys = h[kResKeys];
+  plan->key_bytes = h[kResKeyBytes];
+  plan->token_bytes = h[kResTokenBytes];
+  plan->n_bytes = align16(h[kResBlobBytes]) + h[kResKeyBytes];
+  // crr_blob_wf, the seeds and the descriptors' token offsets index with 32 bits
+  return h[kResBlobs] < 0xFFFFFFFFull && h[kResKeys] <= 0xFFFFFFFFull && h[kResTokenBytes] <= 0xFFFFFFFFull ? 0 : -1;
+}
+
+// the plan as a call after it may use it: its work buffer laid out for the planned batch
+static bool resume_plan_usable(const crr_load_resume_sizes* P, uint32_t n_wf, const void* work, size_t work_bytes) {
+  if (!P || P->err != 0 || P->n_wf != n_wf) return false;
+  const ResumeLayout L = carve_resume(n_wf);
+  if (P->work_needed != L.end) return false;
+  if (n_wf && (!work || ((uintptr_t)work & 15u) || L.end > work_bytes)) return false;
+  return P->n_blobs < 0xFFFFFFFFull && P->n_keys <= 0xFFFFFFFFull && P->token_bytes <= 0xFFFFFFFFull &&
+         P->n_bytes == align16(P->blob_bytes) + P->key_bytes && P->n_applied <= n_wf;
+}
+
+int crr_load_resume_gather(const crr_state_batch* in, const void* scratch, size_t scratch_bytes,
+                           const crr_load_summary* summary_host, const crr_repl_task* tasks,
+                           const crr_blob_batch* task_blobs, const crr_load_resume_row* rows, const void* work,
+                           size_t work_bytes, const crr_load_resume_sizes* plan_host, const crr_load_resume_out* out,
+                           void* stream) {
+  Ctx c;
+  ResumeIn r;
+  ResumeWork k;
+  if (!plan_host || !out || !in || !resume_plan_usable(plan_host, in->n_wf, work, work_bytes)) return -1;
+  const crr_load_resume_sizes& P = *plan_host;
+  (void)rows;   // (neither the rows nor the routes are read again: the winners are in `work`)
+  if (resume_setup(in, scratch, scratch_bytes, summary_host, tasks, nullptr, P.n_tasks, task_blobs, work, c, r, k) != 0) return -1;
+  auto usable = [](const void* p, uint64_t capacity, uint64_t total, uintptr_t align) {
+    return capacity >= total && (total == 0 || (p && !((uintptr_t)p & align)));
+  };
+  if (!usable(out->bytes, out->bytes_capacity, P.n_bytes, 15u)) return -1;
+  if (!out->blob_off || ((uintptr_t)out->blob_off & 7u) || out->blob_capacity < P.n_blobs) return -1;
+  if (!usable(out->key_off, out->key_capacity, P.n_keys, 7u) || !usable(out->key_len, out->key_capacity, P.n_keys, 3u)) return -1;
+  if (in->n_wf && (!out->wf || ((uintptr_t)out->wf & 7u) || !out->key_begin || !out->key_count || !out->task_of)) return -1;
+  const uint64_t n_chunks = (P.n_bytes + 15) / 16, blocks = (n_chunks + kBlock - 1) / kBlock;
+  if (n_chunks < P.n_bytes / 16 || blocks > 0x7FFFFFFFull) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  hipError_t e;
+  if (in->n_wf == 0) return (int)hipMemsetAsync(out->blob_off, 0, sizeof(uint64_t), s);
+  const ResumeTotals T = {P.n_blobs, P.blob_bytes, P.n_keys, P.key_bytes, P.n_bytes};
+  uint64_t longest = in->n_wf;
+  if (P.n_blobs + 1 > longest) longest = P.n_blobs + 1;
+  if (P.n_keys > longest) longest = P.n_keys;
+  hipLaunchKernelGGL(load_resume_index_kernel, dim3((uint32_t)((longest + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, r, k, T,
+                     *out);
+  if (n_chunks)
+    hipLaunchKernelGGL(load_resume_gather_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, c, r, k, T, n_chunks, out->bytes);
+  e = hipGetLastError();
+  return (int)e;
+}
+
+int crr_load_resume_finalize(const void* scratch, size_t scratch_bytes, const crr_load_summary* summary_host,
+                             const crr_blob_wf* gathered_wf, const int32_t* counts, uint64_t count_stride, void* work,
+                             size_t work_bytes, const crr_load_resume_sizes* plan_host, crr_workflow* wf, uint8_t* arena,
+                             size_t arena_capacity, crr_load_resume_totals* totals, void* stream) {
+  Ctx c;
+  if (!summary_host || !totals || !resume_plan_usable(plan_host, summary_host->n_wf, work, work_bytes)) return -1;
+  const crr_load_resume_sizes& P = *plan_host;
+  const uint32_t n_wf = P.n_wf;
+  if ((uint64_t)arena_capacity < P.token_bytes || (P.token_bytes && !arena)) return -1;
+  if (n_wf) {
+    if (!plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
+    if (!gathered_wf || !counts || count_stride < n_wf || !wf || ((uintptr_t)wf & 7u) || ((uintptr_t)gathered_wf & 7u)) return -1;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_wf == 0) {
+    memset(totals, 0, sizeof *totals);
+    return 0;
+  }
+  ResumeWork k;
+  k.s = static_cast<uint8_t*>(work);
+  k.L = carve_resume(n_wf);
+  k.n_wf = n_wf;
+  hipLaunchKernelGGL(load_resume_caps_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, c, k, counts, count_stride);
+  hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, k.cap_sums(), k.L.n_blocks, kResCaps, k.cap_totals());
+  hipLaunchKernelGGL(load_resume_descriptor_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, c, k, gathered_wf, counts,
+                     count_stride, wf, arena, (uint64_t)arena_capacity);
+  hipError_t e;
+  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  uint64_t h[kResCaps];
+  if ((e = hipMemcpyAsync(h, k.cap_totals(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  memset(totals, 0, sizeof *totals);
+  totals->arena_bytes = P.token_bytes;
+  for (int t = 0; t < kResCaps; ++t) totals->table_rows[t] = h[t];
+  return 0;
+}
+
+int crr_load_resume_settle(const int32_t* task_of, crr_workflow* wf, uint32_t n_wf, void* stream) {
+  if (n_wf && (!task_of || !wf || ((uintptr_t)task_of & 3u) || ((uintptr_t)wf & 7u))) return -1;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  crr_internal::StreamDevice on_dev_(s);
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  if (n_wf == 0) return 0;
+  hipLaunchKernelGGL(load_resume_settle_kernel, grid_of(n_wf), dim3(kBlock), 0, s, task_of, wf, n_wf);
   return (int)hipGetLastError();
 }
 

@@ -7,7 +7,8 @@
 // crr_load_store_checksums_host (include/cadence_load_store.h) both, then load_decode.h's store_task per task;
 // crr_load_store_vh_host (include/cadence_load_store_vh.h) the same, then its sizes and its sequential blob writer;
 // crr_load_mutation_host (include/cadence_load_mutation.h) the same, then its count and emit passes and the gather;
-// crr_load_store_exec_host (include/cadence_load_store_exec.h) the same, then its decision and its splice per task.
+// crr_load_store_exec_host (include/cadence_load_store_exec.h) the same, then its decision and its splice per task;
+// crr_load_resume_host (include/cadence_load_resume.h) the load, then its decisions, serial prefixes and the gather.
 #include <stdlib.h>
 
 #include <thread>
@@ -516,6 +517,120 @@ extern "C" int crr_load_store_exec_host(const crr_state_batch* in, const crr_rep
   }
   free(vh_bytes), free(vh_rows), free(vh_off), free(my_rows), free(my_off);
   free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
+  free(k.s);
+  free(c.s);
+  return ret;
+}
+
+// the resumed replay of routed tasks planned from the loaded states (include/cadence_load_resume.h): the same load,
+// then load_decode.h's decisions over a work buffer laid out like the device's -- the bids as a loop that keeps the
+// lowest index, the prefixes as serial scans, the byte gather chunk by chunk through the device's own function
+extern "C" int crr_load_resume_host(const crr_state_batch* in, const crr_repl_task* tasks, const crr_ndc_route* routes,
+                                    uint32_t n_tasks, const crr_blob_batch* task_blobs, const int32_t* counts,
+                                    crr_load_resume_row* rows, const crr_load_resume_out* out, crr_workflow* wf,
+                                    uint8_t* arena, size_t arena_capacity, crr_load_resume_sizes* plan,
+                                    crr_load_resume_totals* totals, int threads) {
+  if (!in || !plan || (n_tasks && (!tasks || !routes || !task_blobs))) return -1;
+  if (task_blobs && ((task_blobs->n_wf && !task_blobs->wf) || !task_blobs->blob_off || (task_blobs->n_blobs && !task_blobs->bytes)))
+    return -1;
+  Ctx c;
+  const int rc = run_load(in, threads, c);
+  if (rc != 0) return rc;
+  const uint32_t n_wf = in->n_wf;
+  ResumeIn r;
+  memset(&r, 0, sizeof r);
+  r.tasks = tasks;
+  r.routes = routes;
+  r.n_tasks = n_tasks;
+  if (task_blobs) {
+    r.tb_bytes = task_blobs->bytes;
+    r.tb_off = task_blobs->blob_off;
+    r.tb_wf = task_blobs->wf;
+    r.tb_n_blobs = task_blobs->n_blobs;
+    r.tb_n_wf = task_blobs->n_wf;
+  }
+  ResumeWork k;
+  k.L = carve_resume(n_wf);
+  k.n_wf = n_wf;
+  k.s = static_cast<uint8_t*>(calloc(k.L.end + 16, 1));
+  if (!k.s) {
+    free(c.s);
+    return -2;
+  }
+  int ret = 0;
+  memset(k.winner(), 0xFF, (size_t)n_wf * sizeof(uint32_t));
+  for (uint32_t i = n_tasks; i-- > 0;)   // descending: the lowest index is written last
+    if (resume_candidate(c, r, i) == CRR_RESUME_APPLIED) k.winner()[tasks[i].wf] = i;
+  uint64_t run[kResCols] = {0, 0, 0, 0, 0, 0};
+  for (uint32_t p = 0; p < n_wf; ++p) {
+    uint64_t v[kResCols];
+    resume_counts(c, r, k.winner()[p], p, v);
+    for (int col = 0; col < kResCols; ++col) {
+      k.off(col)[p] = run[col];
+      run[col] += v[col];
+    }
+  }
+  for (int col = 0; col < kResCols; ++col) k.off(col)[n_wf] = run[col];
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  plan->n_wf = n_wf;
+  plan->n_applied = run[kResApplied];
+  plan->n_blobs = run[kResBlobs];
+  plan->blob_bytes = run[kResBlobBytes];
+  plan->n_keys = run[kResKeys];
+  plan->key_bytes = run[kResKeyBytes];
+  plan->token_bytes = run[kResTokenBytes];
+  plan->n_bytes = align16(run[kResBlobBytes]) + run[kResKeyBytes];
+  plan->work_needed = k.L.end;
+  if (run[kResBlobs] >= 0xFFFFFFFFull || run[kResKeys] > 0xFFFFFFFFull || run[kResTokenBytes] > 0xFFFFFFFFull) ret = -1;
+  if (totals) {
+    memset(totals, 0, sizeof *totals);
+    totals->arena_bytes = plan->token_bytes;
+  }
+  if (ret == 0 && out) {
+    bool ok = out->bytes_capacity >= plan->n_bytes && (plan->n_bytes == 0 || out->bytes) && out->blob_off &&
+              out->blob_capacity >= plan->n_blobs && out->key_capacity >= plan->n_keys &&
+              (plan->n_keys == 0 || (out->key_off && out->key_len));
+    if (n_wf && (!out->wf || !out->key_begin || !out->key_count || !out->task_of)) ok = false;
+    if (!ok) ret = -1;   // nothing written
+  }
+  if (ret == 0 && (wf || arena) && (uint64_t)arena_capacity < plan->token_bytes) ret = -1;
+  if (ret == 0 && rows)
+    for (uint32_t i = 0; i < n_tasks; ++i) rows[i] = resume_row(c, r, k.winner(), i);
+  const ResumeTotals T = {plan->n_blobs, plan->blob_bytes, plan->n_keys, plan->key_bytes, plan->n_bytes};
+  if (ret == 0 && out) {
+    for (uint32_t p = 0; p < n_wf; ++p) {
+      out->wf[p] = resume_blob_wf(r, k, p);
+      out->key_begin[p] = (uint32_t)k.off(kResKeys)[p];
+      out->key_count[p] = (uint32_t)(k.off(kResKeys)[p + 1] - k.off(kResKeys)[p]);
+      const uint32_t task = k.winner()[p];
+      out->task_of[p] = task == kResNoTask ? -1 : (int32_t)task;
+    }
+    for (uint64_t j = 0; j <= T.n_blobs; ++j) out->blob_off[j] = n_wf ? resume_blob_off(r, k, T, j) : 0;
+    for (uint64_t e = 0; e < T.n_keys; ++e) resume_key(c, k, T, e, out->key_off[e], out->key_len[e]);
+    const uint64_t n_chunks = (T.n_bytes + 15) / 16;
+    for (uint64_t i = 0; i < n_chunks; ++i) {
+      uint64_t lo, hi;
+      resume_gather_chunk(c, r, k, T, i, lo, hi);
+      const uint64_t n = T.n_bytes - 16 * i < 16 ? T.n_bytes - 16 * i : 16;
+      for (uint64_t b = 0; b < n; ++b) out->bytes[16 * i + b] = (uint8_t)((b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8))) & 0xffu);
+    }
+  }
+  if (ret == 0 && counts && wf && out && n_wf) {
+    if (plan->token_bytes && !arena) {
+      ret = -1;
+    } else {
+      uint64_t base[kResCaps] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (uint32_t p = 0; p < n_wf; ++p) {
+        uint64_t cap[kResCaps];
+        resume_caps(c, k, counts, n_wf, p, cap);
+        wf[p] = resume_descriptor(c, k, out->wf, counts, n_wf, p, cap, base, arena, arena_capacity);
+        for (int t = 0; t < kResCaps; ++t) base[t] += cap[t];
+      }
+      if (totals)
+        for (int t = 0; t < kResCaps; ++t) totals->table_rows[t] = base[t];
+    }
+  }
   free(k.s);
   free(c.s);
   return ret;

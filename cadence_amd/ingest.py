@@ -225,6 +225,7 @@ class DeviceIngest:
         torch = self.torch
         s = stream if stream is not None else torch.cuda.current_stream(self.eng.dev)
         cap = max_events if max_events is not None else max(4096, db.blobs.n_bytes // 40)
+        self.replans = 0          # how often this call grew the scratch and planned again
         while True:
             size = self.ensure_scratch(db, cap)
             S = CIngestSummary()
@@ -239,6 +240,7 @@ class DeviceIngest:
                 raise RuntimeError(f"crr_ingest_plan failed: {rc}")
             if S.err == SCRATCH_TOO_SMALL:
                 cap = max(2 * cap, int(S.n_events) + 1)
+                self.replans += 1
                 continue
             if S.err and (db.pending is None or int(S.err_blob) < db.pending[1]):
                 raise IngestError(int(S.err), int(S.err_blob))
@@ -381,6 +383,7 @@ class _ShellBatch:
     wave_begin: int
     tiers: tuple
     shapes: dict
+    perm = None          # device position p is workflow perm[p] of what was laid out (None: p)
 
     @property
     def n_wf(self) -> int:

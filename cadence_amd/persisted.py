@@ -477,6 +477,8 @@ def _host_lib():
         L.crr_load_mutation_host.restype = ctypes.c_int
         L.crr_load_store_exec_host.argtypes = [vp, vp, vp, ctypes.c_uint32] + [vp] * 9 + [ctypes.c_size_t, vp, ctypes.c_int]
         L.crr_load_store_exec_host.restype = ctypes.c_int
+        L.crr_load_resume_host.argtypes = [vp, vp, vp, ctypes.c_uint32] + [vp] * 6 + [ctypes.c_size_t, vp, vp, ctypes.c_int]
+        L.crr_load_resume_host.restype = ctypes.c_int
         L._load_bound = True
     return L
 
@@ -795,6 +797,126 @@ def store_executions_host(sbs: StateBlobSet, tasks, last_events, results, routes
     return rows, off, out[:int(P.n_bytes)].copy()
 
 
+# ---- the resumed replay of routed tasks planned from loaded states (include/cadence_load_resume.h) ---------------
+@dataclasses.dataclass
+class ResumeImage:
+    """What ``crr_load_resume_plan`` / ``_gather`` / ``_finalize`` (or ``crr_load_resume_host``) produce, on the host:
+    the per-task rows, the gathered blob batch with its seeds and ``task_of``, and -- once the inserts of this call
+    are known -- the descriptors, the token arena and the slot-table totals."""
+    sizes: abi.CLoadResumeSizes
+    rows: np.ndarray                      # abi.LOAD_RESUME_ROW [n_tasks]
+    bytes: np.ndarray                     # uint8 [n_bytes]
+    blob_off: np.ndarray                  # uint64 [n_blobs + 1]
+    wf: np.ndarray                        # blobs.BLOB_WF [n_wf]
+    key_begin: np.ndarray
+    key_count: np.ndarray
+    key_off: np.ndarray                   # uint64 [n_keys] into ``bytes``
+    key_len: np.ndarray
+    task_of: np.ndarray                   # int32 [n_wf], -1: no task
+    desc: Optional[np.ndarray] = None     # abi.WORKFLOW [n_wf]
+    arena: Optional[np.ndarray] = None    # uint8 [token_bytes]
+    table_rows: Optional[List[int]] = None
+
+    def blob(self, j: int) -> bytes:
+        return self.bytes[int(self.blob_off[j]):int(self.blob_off[j + 1])].tobytes()
+
+    def keys(self, p: int) -> List[str]:
+        """Position p's seeded strings, key id k at index k - 1."""
+        b, n = int(self.key_begin[p]), int(self.key_count[p])
+        return [self.bytes[int(self.key_off[e]):int(self.key_off[e]) + int(self.key_len[e])].tobytes().decode()
+                for e in range(b, b + n)]
+
+    def token(self, p: int) -> bytes:
+        o = int(self.desc[p]["start_token_off"])
+        return self.arena[o:o + int(self.desc[p]["start_token_len"])].tobytes()
+
+    def blob_set(self, strings: np.ndarray):
+        """The gathered batch as a ``blobs.BlobSet`` (``strings``: the task batch's)."""
+        from .blobs import BlobSet
+        data = np.concatenate([self.bytes, np.zeros(abi.INGEST_PAD, np.uint8)])
+        return BlobSet(bytes=data, blob_off=self.blob_off.copy(), wf=self.wf.copy(), strings=strings)
+
+    def image_bytes(self) -> Dict[str, bytes]:
+        """Every buffer as bytes (host against device comparisons)."""
+        out = {f: getattr(self, f).tobytes() for f in ("rows", "bytes", "blob_off", "wf", "key_begin", "key_count",
+                                                         "key_off", "key_len", "task_of")}
+        out["sizes"] = bytes(self.sizes)[4:]          # (err apart)
+        if self.desc is not None:
+            out.update(desc=self.desc.tobytes(), arena=self.arena.tobytes(), table_rows=repr(self.table_rows).encode())
+        return out
+
+
+class _ResumeBuffers:
+    """Host buffers of a ``crr_load_resume_out`` sized exactly from a plan."""
+
+    def __init__(self, P: abi.CLoadResumeSizes):
+        from .blobs import BLOB_WF
+        n = int(P.n_wf)
+        self.bytes = np.zeros(int(P.n_bytes), np.uint8)
+        self.blob_off = np.zeros(int(P.n_blobs) + 1, np.uint64)
+        self.wf = np.zeros(n, BLOB_WF)
+        self.key_begin, self.key_count = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self.key_off, self.key_len = np.zeros(int(P.n_keys), np.uint64), np.zeros(int(P.n_keys), np.uint32)
+        self.task_of = np.zeros(n, np.int32)
+        self.c = abi.CLoadResumeOut()
+
+        def ptr(a):
+            return a.ctypes.data if a.size else None
+        for f in ("bytes", "blob_off", "wf", "key_begin", "key_count", "key_off", "key_len", "task_of"):
+            setattr(self.c, f, ptr(getattr(self, f)))
+        self.c.bytes_capacity, self.c.blob_capacity, self.c.key_capacity = int(P.n_bytes), int(P.n_blobs), int(P.n_keys)
+
+
+def resume_counts_of(batch: HistoryBatch) -> np.ndarray:
+    """The int32 ``[RESUME_COUNT_ROWS, n_wf]`` counts ``crr_load_resume_host`` takes, from a canonical batch of this
+    call's events alone (``decode.decode_histories`` of the gathered blobs, or ``flatten`` without ``loaded``): its
+    capacities are this call's inserts."""
+    out = np.zeros((abi.RESUME_COUNT_ROWS, batch.n_wf), np.int32)
+    out[0], out[1] = batch.wf["ev_count"], batch.wf["empty_batch_at"]
+    for t, (_name, _dt, _base, cap_f, _n) in enumerate(abi.TABLES):
+        out[2 + t] = batch.wf[cap_f]
+    return out
+
+
+def load_resume_host(sbs: StateBlobSet, tasks, routes, task_blobs, counts: Optional[np.ndarray] = None,
+                     threads: int = 1) -> ResumeImage:
+    """Plan the resumed replay of ``tasks`` onto the states of ``sbs`` with the host restatement
+    (``crr_load_resume_host``): ``routes`` ``abi.NDC_ROUTE`` per task, ``task_blobs`` a ``blobs.BlobSet`` whose
+    workflow k holds task k's event blobs; ``counts`` (``resume_counts_of``) adds the descriptors, the arena and the
+    totals."""
+    L = _host_lib()
+    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    tasks = np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
+    routes = np.ascontiguousarray(routes, dtype=abi.NDC_ROUTE)
+    n = int(tasks.shape[0])
+    if routes.shape != (n,):
+        raise ValueError(f"{routes.shape} routes for {n} tasks")
+    tb = _c_task_blobs(task_blobs, lambda a: a.ctypes.data if a.size else None)
+    P, Q = abi.CLoadResumeSizes(), abi.CLoadResumeTotals()
+    cnt = None
+    if counts is not None:
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (abi.RESUME_COUNT_ROWS, sbs.n_wf):
+            raise ValueError(f"{cnt.shape} counts for {sbs.n_wf} workflows")
+
+    def ptr(a):
+        return a.ctypes.data if a is not None and a.size else None
+
+    def call(rows, out, wf, arena, cap):
+        rc = L.crr_load_resume_host(ctypes.byref(c), ptr(tasks), ptr(routes), n, ctypes.byref(tb), ptr(cnt), rows, out, wf,
+                                    arena, cap, ctypes.byref(P), ctypes.byref(Q), threads)
+        if rc != 0:
+            raise RuntimeError(f"crr_load_resume_host failed: {rc}")
+    call(None, None, None, None, 0)   # sizes
+    rows = np.zeros(n, abi.LOAD_RESUME_ROW)
+    buf = _ResumeBuffers(P)
+    desc = np.zeros(sbs.n_wf, abi.WORKFLOW) if cnt is not None else None
+    arena = np.zeros(int(P.token_bytes), np.uint8) if cnt is not None else None
+    call(ptr(rows), ctypes.byref(buf.c), ptr(desc), ptr(arena), int(P.token_bytes))
+    return ResumeImage(P, rows, buf.bytes, buf.blob_off, buf.wf, buf.key_begin, buf.key_count, buf.key_off, buf.key_len,
+                       buf.task_of, desc, arena, [int(x) for x in Q.table_rows] if cnt is not None else None)
+
+
 def _struct_fields(raw: bytes) -> Dict[int, bytes]:
     """The top-level fields of a thrift-binary struct whose fields are scalars, binaries, list<binary> or
     map<binary, binary> (the six state structs): field id -> the bytes of a binary field, b"" for any other."""
@@ -1019,6 +1141,20 @@ class StateLoader:
         L.crr_load_store_exec_run.argtypes = ([vp, vp, ctypes.c_size_t, vp, vp, vp] + [vp] * 15 +
                                               [ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp])
         L.crr_load_store_exec_run.restype = ctypes.c_int
+        L.crr_load_resume_scratch_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        L.crr_load_resume_scratch_bytes.restype = ctypes.c_size_t
+        L.crr_load_resume_plan.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_size_t, vp, vp]
+        L.crr_load_resume_plan.restype = ctypes.c_int
+        L.crr_load_resume_gather.argtypes = [vp, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]
+        L.crr_load_resume_gather.restype = ctypes.c_int
+        L.crr_load_resume_finalize.argtypes = [vp, ctypes.c_size_t, vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_size_t, vp, vp, vp,
+                                               ctypes.c_size_t, vp, vp]
+        L.crr_load_resume_finalize.restype = ctypes.c_int
+        L.crr_load_resume_settle.argtypes = [vp, vp, ctypes.c_uint32, vp]
+        L.crr_load_resume_settle.restype = ctypes.c_int
+        L.crr_ingest_resume_counts.argtypes = [vp, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p),
+                                               ctypes.POINTER(ctypes.c_uint64)]
+        L.crr_ingest_resume_counts.restype = ctypes.c_int
         self.last_ndc = None
         self.scratch = None
         self.scratch_bytes = 0
@@ -1352,6 +1488,190 @@ class StateLoader:
         return m.rows, m
 
 
+    # ---- include/cadence_load_resume.h ---------------------------------------------------------------------
+    def resume_plan(self, ds: DeviceStates, tasks, task_blobs) -> "ResumePlan":
+        """Decide which task is applied onto which loaded state and size the gather (``crr_load_resume_plan``, one
+        synchronisation) for the ``tasks`` (``abi.REPL_TASK``) the last ``ndc_prepare`` routed -- the routes stay on the
+        device.  ``task_blobs``: the tasks' event blobs resident in HBM (an ``ingest.DeviceBlobs`` whose workflow k is
+        task k).  The rows and the work buffer stay on the device; ``plan.sizes`` holds the totals."""
+        from .engine import _dev_bytes
+        if self.last_ndc is None:
+            raise RuntimeError("resume_plan: no ndc_prepare to take the routes from")
+        if getattr(task_blobs, "pending", None) is not None:
+            # a transcoded task batch with a rejected blob: the gather would drop the rejection with the blob's index
+            from .ingest import IngestError
+            raise IngestError(*task_blobs.pending)
+        torch, dev = self.torch, self.engine.dev
+        br, out = self.last_ndc
+        tasks = np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
+        n, n_wf = int(tasks.shape[0]), int(ds.c.n_wf)
+        if n > int(br.plan.n_tasks):
+            raise ValueError(f"{n} tasks, {int(br.plan.n_tasks)} routed")
+        work_bytes = int(self.lib.crr_load_resume_scratch_bytes(n_wf, n))
+        T = {"tasks": _dev_bytes(torch, tasks, dev),
+             "rows": torch.empty(max(n, 1) * abi.LOAD_RESUME_ROW.itemsize, dtype=torch.uint8, device=dev),
+             "work": torch.empty(work_bytes + 16, dtype=torch.uint8, device=dev), "routes": out["routes"]}
+        P = abi.CLoadResumeSizes()
+        vp = ctypes.c_void_p
+        rc = self.lib.crr_load_resume_plan(ctypes.byref(ds.c), vp(self.scratch.data_ptr() if self.scratch is not None else None),
+                                           ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
+                                           vp(T["tasks"].data_ptr()), vp(out["routes"].data_ptr()), n,
+                                           ctypes.byref(task_blobs.c), vp(T["rows"].data_ptr()), vp(T["work"].data_ptr()),
+                                           ctypes.c_size_t(work_bytes), ctypes.byref(P), self._stream())
+        if rc != 0 or P.err != 0:
+            raise RuntimeError(f"crr_load_resume_plan failed: {rc} (err {P.err})")
+        T["work_bytes"] = work_bytes
+        return ResumePlan(n, P, T, ds, task_blobs)
+
+    @staticmethod
+    def resume_out_sizes(P: abi.CLoadResumeSizes) -> Dict[str, int]:
+        """Bytes of each output of ``resume_gather`` for a plan (``bytes`` without the readable pad)."""
+        from .blobs import BLOB_WF
+        n = int(P.n_wf)
+        return {"bytes": int(P.n_bytes), "blob_off": (int(P.n_blobs) + 1) * 8, "wf": n * BLOB_WF.itemsize, "key_begin": n * 4,
+                "key_count": n * 4, "key_off": int(P.n_keys) * 8, "key_len": int(P.n_keys) * 4, "task_of": n * 4}
+
+    def resume_gather(self, plan: "ResumePlan", out=None, capacity=None):
+        """Write the gathered blob batch, the seeds and ``task_of`` (``crr_load_resume_gather``, enqueued on the current
+        stream).  ``out``: device uint8 tensors by ``resume_out_sizes``' names (default: each of exactly the plan's size,
+        ``bytes`` with ``INGEST_PAD`` readable bytes behind it); ``capacity``: ``bytes`` / ``blobs`` / ``keys`` that may be
+        written (default: the plan's totals).  Returns the tensors.  Too small a capacity raises and launches nothing."""
+        torch, dev, P = self.torch, self.engine.dev, plan.sizes
+        size = self.resume_out_sizes(P)
+        out = dict(out or {})
+        for f, nb in size.items():
+            if f not in out:
+                out[f] = torch.empty(max(nb, 1) + (abi.INGEST_PAD + 16 if f == "bytes" else 16), dtype=torch.uint8, device=dev)
+        cap = {"bytes": int(P.n_bytes), "blobs": int(P.n_blobs), "keys": int(P.n_keys)}
+        cap.update(capacity or {})
+        o = abi.CLoadResumeOut()
+        for f in size:
+            setattr(o, f, out[f].data_ptr())
+        o.bytes_capacity, o.blob_capacity, o.key_capacity = cap["bytes"], cap["blobs"], cap["keys"]
+        T, ds = plan.tensors, plan.ds
+        vp = ctypes.c_void_p
+        rc = self.lib.crr_load_resume_gather(ctypes.byref(ds.c), vp(self.scratch.data_ptr() if self.scratch is not None else None),
+                                             ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
+                                             vp(T["tasks"].data_ptr()), ctypes.byref(plan.task_blobs.c), vp(T["rows"].data_ptr()),
+                                             vp(T["work"].data_ptr()), ctypes.c_size_t(T["work_bytes"]), ctypes.byref(P),
+                                             ctypes.byref(o), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_resume_gather failed: {rc}")
+        T["out"] = out
+        self.last_resume = plan   # alive until the stream has run the kernels
+        return out
+
+    def resume_blobs(self, plan: "ResumePlan"):
+        """The gathered batch of the last ``resume_gather`` of ``plan`` as an ``ingest.DeviceBlobs`` (the strings and
+        the known domains are the task batch's) and the ``ingest.CIngestResume`` naming its seeds; the descriptors
+        ``crr_load_resume_finalize`` writes and ``crr_ingest_layout_resume`` continues in place are ``tensors["desc"]``."""
+        from .ingest import CBlobBatch, CIngestResume, DeviceBlobs, _TranscodedShape
+        P, T = plan.sizes, plan.tensors
+        out = T["out"]
+        c = CBlobBatch.from_buffer_copy(plan.task_blobs.c)
+        c.bytes, c.blob_off, c.wf = out["bytes"].data_ptr(), out["blob_off"].data_ptr(), out["wf"].data_ptr()
+        c.n_blobs, c.n_wf = int(P.n_blobs), int(P.n_wf)
+        if "desc" not in T:
+            T["desc"] = self.torch.zeros(max(int(P.n_wf), 1) * abi.WORKFLOW.itemsize + 16, dtype=self.torch.uint8, device=self.engine.dev)
+        R = CIngestResume()
+        R.loaded_wf, R.wave_begin = T["desc"].data_ptr(), 0
+        for f in ("key_begin", "key_count", "key_off", "key_len"):
+            setattr(R, f, out[f].data_ptr())
+        tensors = dict(plan.task_blobs.tensors)
+        tensors.update(bytes=out["bytes"], blob_off=out["blob_off"], wf=out["wf"])
+        return DeviceBlobs(_TranscodedShape(int(P.n_bytes), int(P.n_blobs), int(P.n_wf)), tensors, c), R
+
+    def resume_finalize(self, plan: "ResumePlan", gdb, ingest, arena=None) -> abi.CLoadResumeTotals:
+        """The descriptors and the token arena (``crr_load_resume_finalize``, one synchronisation) once ``ingest`` has
+        planned the gathered batch ``gdb`` (``crr_ingest_plan_resume``): ``plan.tensors["desc"]`` / ``["arena"]``
+        (``arena``: a device uint8 tensor of at least ``token_bytes`` to write instead of a fresh one)."""
+        torch, dev, P, T = self.torch, self.engine.dev, plan.sizes, plan.tensors
+        counts, stride = ctypes.c_void_p(), ctypes.c_uint64()
+        vp = ctypes.c_void_p
+        rc = self.lib.crr_ingest_resume_counts(ctypes.byref(gdb.c), vp(ingest.scratch.data_ptr()), ctypes.c_size_t(ingest.scratch_bytes),
+                                               ctypes.byref(counts), ctypes.byref(stride))
+        if rc != 0:
+            raise RuntimeError(f"crr_ingest_resume_counts failed: {rc}")
+        T["arena"] = arena if arena is not None else torch.zeros(int(P.token_bytes) + 16, dtype=torch.uint8, device=dev)
+        Q = abi.CLoadResumeTotals()
+        rc = self.lib.crr_load_resume_finalize(vp(self.scratch.data_ptr() if self.scratch is not None else None),
+                                               ctypes.c_size_t(self.scratch_bytes), ctypes.byref(self.summary),
+                                               vp(T["out"]["wf"].data_ptr()), counts, stride, vp(T["work"].data_ptr()),
+                                               ctypes.c_size_t(T["work_bytes"]), ctypes.byref(P), vp(T["desc"].data_ptr()),
+                                               vp(T["arena"].data_ptr()), ctypes.c_size_t(int(P.token_bytes)), ctypes.byref(Q),
+                                               self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_resume_finalize failed: {rc}")
+        plan.totals = Q
+        return Q
+
+    def resume(self, ds: DeviceStates, tasks, task_blobs, ingest, emit_tasks: bool = False, max_events: Optional[int] = None):
+        """The resumed replay of the routed ``tasks`` onto the last plan's states, laid out on the device: plan, gather,
+        ``crr_ingest_plan_resume`` over the gathered batch, finalize, the outputs allocated, the loaded rows placed,
+        ``crr_ingest_layout_resume``, ``crr_load_resume_settle``.  Returns an ``engine.DeviceBatch`` ready for ``engine.launch`` (canonical layout:
+        device position p is loaded workflow p), which the store methods take as ``db=``; ``self.last_resume`` keeps
+        the plan.  ``max_events``: the event capacity the ingest scratch is first sized for (``DeviceIngest.plan``).  A
+        task blob the decoder rejects raises ``ingest.IngestError`` with the task's index as ``.task``; nothing is
+        enqueued after it."""
+        from .engine import DeviceBatch
+        from .ingest import IngestError, _ShellBatch
+        torch, dev = self.torch, self.engine.dev
+        plan = self.resume_plan(ds, tasks, task_blobs)
+        self.resume_gather(plan)
+        gdb, R = self.resume_blobs(plan)
+        try:
+            S = ingest.plan(gdb, resume=R, max_events=max_events)
+        except IngestError as e:
+            from .blobs import BLOB_WF
+            n = int(plan.sizes.n_wf)
+            out = plan.tensors["out"]
+            begin = out["wf"][:n * BLOB_WF.itemsize].cpu().numpy().view(BLOB_WF)["blob_begin"].astype(np.int64)
+            task_of = out["task_of"][:n * 4].cpu().numpy().view(np.int32)
+            p = int(np.searchsorted(begin, e.blob, side="right")) - 1     # the last position whose range starts at or before it
+            task = int(task_of[p]) if 0 <= p < n else -1
+            err = IngestError(e.code, e.blob)
+            err.task = task
+            err.args = (f"{e.args[0]}: task {task}",)
+            raise err from None
+        Q = self.resume_finalize(plan, gdb, ingest)
+        n = int(plan.sizes.n_wf)
+        T = plan.tensors
+        ci = abi.CInputs()
+        T["wf"] = T["desc"]                                # the layout continues the descriptors in place
+        ingest.allocate_inputs(S, T, ci, wf_in_place=T["desc"])
+        ci.arena = T["arena"].data_ptr()
+        ci.n_wf, ci.stride, ci.wave_begin, ci.big_begin = n, 1, 0, n
+        ci.flags = (abi.IN_HAS_NEW_RUN if S.has_new_run else 0) | (abi.IN_EMIT_TASKS if emit_tasks else 0)
+        co = abi.COutputs()
+        T["exec"] = torch.zeros(max(n, 1) * abi.EXEC_ROW.itemsize, dtype=torch.uint8, device=dev)
+        co.exec = T["exec"].data_ptr()
+        table_rows = {}
+        for j, (name, dt, *_r) in enumerate(abi.TABLES):
+            table_rows[name] = int(Q.table_rows[j])
+            rows = 1 if name == "tasks" and not emit_tasks else max(table_rows[name], 1)
+            T["out_" + name] = torch.zeros(rows * dt.itemsize, dtype=torch.uint8, device=dev)
+            setattr(co, name, T["out_" + name].data_ptr())
+        T["scratch"] = torch.zeros(2 * n + abi.SCRATCH_EXTRA_WORDS, dtype=torch.int32, device=dev)
+        co.scratch = T["scratch"].data_ptr()
+        for t, name in enumerate(abi.ID_TABLES):
+            T["ids_" + name] = torch.zeros(max(table_rows[name], 1), dtype=torch.int64, device=dev)
+            co.live_ids[t] = T["ids_" + name].data_ptr()
+        T["perm"] = torch.arange(max(n, 1), dtype=torch.int32, device=dev)
+        shapes = ingest.input_shapes(S)
+        shapes["arena"] = int(plan.sizes.token_bytes)
+        shell = _ShellBatch(n, emit_tasks, table_rows, 0, (0, 0, 0, 0, 0, n), shapes)
+        db = DeviceBatch(shell, T, ci, co, self.engine.device)
+        self.place(db)
+        ingest.layout_resume(gdb, R, S, ci)
+        # the layout sets the RESUME flag on every descriptor it continues; a position without a task stays a workflow
+        # without events that resumes nothing
+        rc = self.lib.crr_load_resume_settle(ctypes.c_void_p(T["out"]["task_of"].data_ptr()), ctypes.c_void_p(T["desc"].data_ptr()),
+                                             n, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"crr_load_resume_settle failed: {rc}")
+        T["gathered"], T["resume"], T["summary"] = gdb, R, S
+        return db
+
     # ---- include/cadence_load_store_exec.h -----------------------------------------------------------------
     def store_executions_plan(self, vh_plan: "VhBlobPlan", exec_tasks, task_blobs=None) -> "ExecBlobPlan":
         """Decide, size and script (``crr_load_store_exec_plan``, one synchronisation) the execution blobs of the tasks
@@ -1422,6 +1742,41 @@ class StateLoader:
         return ((plan.rows(), T["blob_off"].cpu().numpy().view(np.uint64).copy(), out[:int(plan.sizes.n_bytes)].cpu().numpy().copy()),
                 (V["rows"][:n * abi.VH_BLOB_ROW.itemsize].cpu().numpy().view(abi.VH_BLOB_ROW).copy(),
                  V["blob_off"].cpu().numpy().view(np.uint64).copy(), vh_out[:int(vh_plan.sizes.n_bytes)].cpu().numpy().copy()))
+
+
+@dataclasses.dataclass
+class ResumePlan:
+    """A finished ``crr_load_resume_plan``: the host sizes, the device rows and work buffer, the states and the task
+    blobs it was made for; ``resume_gather`` adds its output tensors, ``resume`` the descriptors and the arena."""
+    n: int
+    sizes: abi.CLoadResumeSizes
+    tensors: Dict[str, object]
+    ds: DeviceStates
+    task_blobs: object                    # ingest.DeviceBlobs
+    totals: Optional[abi.CLoadResumeTotals] = None
+
+    def rows(self) -> np.ndarray:
+        return self.tensors["rows"][:self.n * abi.LOAD_RESUME_ROW.itemsize].cpu().numpy().view(abi.LOAD_RESUME_ROW).copy()
+
+    def download(self, out=None) -> ResumeImage:
+        """The gather's output tensors (default: the last gather's) copied to the host, exactly the plan's totals of
+        each; with a finished ``resume`` the descriptors, the arena and the totals too."""
+        from .blobs import BLOB_WF
+        P, T = self.sizes, self.tensors
+        out = out if out is not None else T["out"]
+        n = int(P.n_wf)
+
+        def host(f, dt, k):
+            return out[f][:k * np.dtype(dt).itemsize].cpu().numpy().view(dt).copy()
+        img = ResumeImage(P, self.rows(), host("bytes", np.uint8, int(P.n_bytes)), host("blob_off", np.uint64, int(P.n_blobs) + 1),
+                          host("wf", BLOB_WF, n), host("key_begin", np.uint32, n), host("key_count", np.uint32, n),
+                          host("key_off", np.uint64, int(P.n_keys)), host("key_len", np.uint32, int(P.n_keys)),
+                          host("task_of", np.int32, n))
+        if self.totals is not None:
+            img.desc = T["desc"][:n * abi.WORKFLOW.itemsize].cpu().numpy().view(abi.WORKFLOW).copy()
+            img.arena = T["arena"][:int(P.token_bytes)].cpu().numpy().copy()
+            img.table_rows = [int(x) for x in self.totals.table_rows]
+        return img
 
 
 @dataclasses.dataclass

@@ -55,7 +55,8 @@ extern "C" {
  *    CRR_ERR_NDC_STATE_NOT_LOADED; the checksum to store for routed tasks (cadence_load_store.h), crr_sizeof(27 / 28);
  *    the VersionHistories blob to store for them (cadence_load_store_vh.h), crr_sizeof(30 / 31); the pending-entry
  *    mutation to store for them (cadence_load_mutation.h), crr_sizeof(33..35); the execution blob to store for them
- *    (cadence_load_store_exec.h), crr_sizeof(36..38) */
+ *    (cadence_load_store_exec.h), crr_sizeof(36..38); the resumed replay of routed tasks planned from the loaded
+ *    states (cadence_load_resume.h), crr_sizeof(40..43) */
 #define CRR_ABI_VERSION 8
 
 /* ---- constants restated from the reference ------------------------------------------------ */
@@ -644,7 +645,9 @@ size_t crr_sizeof(int which);   /* 0 workflow, 1 exec row, 2 activity, 3 timer, 
                                    25 ndc plan, 26 ndc route, cadence_load_store.h: 27 store row, 28 last event,
                                    cadence_load_store_vh.h: 30 vh blob row, 31 vh blob sizes (29: unassigned, 0),
                                    cadence_load_mutation.h: 33 mutation row, 34 mutation sizes, 35 mutation out (32: unassigned, 0),
-                                   cadence_load_store_exec.h: 36 exec blob task, 37 exec blob row, 38 exec blob sizes */
+                                   cadence_load_store_exec.h: 36 exec blob task, 37 exec blob row, 38 exec blob sizes,
+                                   cadence_load_resume.h: 40 resume row, 41 resume sizes, 42 resume out, 43 resume totals
+                                   (39: unassigned, 0) */
 
 /* Host-side CRC32-IEEE (hash/crc32.ChecksumIEEE) used by the shim's standalone verify. */
 uint32_t crr_crc32_ieee(const uint8_t* data, size_t len);
