@@ -1984,6 +1984,17 @@ struct ExecIn {
   const uint8_t* upserts;
 };
 
+// the tasks' event blobs into the tb_* fields of an ExecIn or a ResumeIn (host code only: the launchers and the host
+// restatement).  It assigns the five fields and checks nothing: what a batch must hold differs from call to call
+template <class In>
+inline void pack_task_blobs(In& x, const crr_blob_batch& B) {
+  x.tb_bytes = B.bytes;
+  x.tb_off = B.blob_off;
+  x.tb_wf = B.wf;
+  x.tb_n_blobs = B.n_blobs;
+  x.tb_n_wf = B.n_wf;
+}
+
 // what the decision leaves for the walk
 struct ExecTask {
   uint32_t active, seen;   // the slots overridden; those of them the stored blob holds

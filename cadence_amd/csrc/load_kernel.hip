@@ -641,6 +641,21 @@ __global__ void __launch_bounds__(kBlock) load_resume_settle_kernel(const int32_
 
 inline dim3 grid_of(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
 
+// every entry point that takes a stream, once its arguments are checked: the stream as `s`, its device selected
+// until the function returns (stream_device.h), or hipErrorInvalidHandle returned
+#define CRR_ON_STREAM(s, stream)                           \
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);   \
+  crr_internal::StreamDevice on_dev_(s);                   \
+  if (!on_dev_.ok) return (int)hipErrorInvalidHandle
+
+// what the launches before it left, then the n totals of a plan on the host: the one synchronisation of a plan call
+inline hipError_t read_totals(hipStream_t s, const uint64_t* dev, uint64_t* host, size_t n) {
+  hipError_t e;
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(host, dev, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  return hipStreamSynchronize(s);
+}
+
 constexpr uint32_t kScanA = 0xFFFu & ~((1u << CRR_LOAD_T_KEYS) | (1u << CRR_LOAD_T_KEY_BYTES));
 constexpr uint32_t kScanB = (1u << CRR_LOAD_T_KEYS) | (1u << CRR_LOAD_T_KEY_BYTES);
 
@@ -666,9 +681,7 @@ int crr_load_states_plan(const crr_state_batch* in, void* scratch, size_t scratc
   if (!in || !summary || !scratch || ((uintptr_t)scratch & 15u)) return -1;
   if (in->n_blobs && (!in->bytes || !in->blob_off || !in->blob)) return -1;
   if (in->n_wf && !in->wf) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   Ctx c;
   c.in = *in;
   c.s = static_cast<uint8_t*>(scratch);
@@ -691,10 +704,8 @@ int crr_load_states_plan(const crr_state_batch* in, void* scratch, size_t scratc
   if (in->n_blobs) hipLaunchKernelGGL(load_parse_kernel, grid_of(in->n_blobs), dim3(kBlock), 0, s, c);
   hipLaunchKernelGGL(load_count_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c);
   hipLaunchKernelGGL(load_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, c, kScanA, d_tot);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[3 + kCounters];
-  if ((e = hipMemcpyAsync(h, c.err(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, c.err(), h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   if (h[2 + kCounters]) return -1;   // blob ranges not consecutive or not covering the blobs
   c.L = carve(in->n_blobs, in->n_wf, h + 2);
   if (c.L.end > scratch_bytes) {
@@ -705,9 +716,7 @@ int crr_load_states_plan(const crr_state_batch* in, void* scratch, size_t scratc
   hipLaunchKernelGGL(load_emit_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c);
   hipLaunchKernelGGL(load_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, c, kScanB, d_tot);
   hipLaunchKernelGGL(load_dict_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  if ((e = hipMemcpyAsync(h, c.err(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, c.err(), h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   int64_t totals[kCounters];
   for (int t = 0; t < kCounters; ++t) totals[t] = (int64_t)h[2 + t];
   fill_summary(summary, c, totals, h[0], h[1], c.L.end);
@@ -728,9 +737,7 @@ int crr_load_states_read(const void* scratch, size_t scratch_bytes, const crr_lo
                          const crr_load_image* dst, void* stream) {
   Ctx c;
   if (!dst || !plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   const crr_load_summary& S = *summary_host;
   const size_t n = S.n_wf;
   if (n == 0) return 0;
@@ -759,9 +766,7 @@ int crr_load_states_place(const void* scratch, size_t scratch_bytes, const crr_l
   int ids = 0;
   for (int t = 0; t < 5; ++t) ids += out->live_ids[t] != nullptr;
   if (ids != 0 && ids != 5) return -1;   // all five set or none
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (layout->n_wf == 0 || summary_host->n_wf == 0) return 0;
   PlaceArgs a;
   a.wf = layout->wf;
@@ -782,9 +787,7 @@ int crr_load_states_verify(const crr_state_batch* in, const void* scratch, size_
   if (!in || !result || !plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
   if (in->n_blobs != summary_host->n_blobs || in->n_wf != summary_host->n_wf) return -1;   // not the planned batch
   if (in->n_blobs && (!in->bytes || !in->blob_off)) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (in->n_wf == 0) return 0;
   c.in = *in;
   hipLaunchKernelGGL(load_verify_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c, stored, invalidate_before_ns, result);
@@ -818,9 +821,7 @@ int crr_load_ndc_plan(const crr_state_batch* in, const void* scratch, size_t scr
   Ctx c;
   NdcWork k;
   if (!plan || (n_tasks && !tasks) || !ndc_usable(in, scratch, scratch_bytes, summary_host, work, n_tasks, c, k)) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   memset(plan, 0, sizeof *plan);
   plan->n_wf = in->n_wf;
   plan->n_tasks = n_tasks;
@@ -844,10 +845,8 @@ int crr_load_ndc_plan(const crr_state_batch* in, const void* scratch, size_t scr
   } else if ((e = hipMemsetAsync(k.out_off(), 0, sizeof(int64_t), s)) != hipSuccess) {
     return (int)e;
   }
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[4];
-  if ((e = hipMemcpyAsync(h, k.totals(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, k.totals(), h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   plan->n_branches = h[0];
   plan->n_items = h[1];
   plan->n_out_items = h[2];
@@ -873,9 +872,7 @@ int crr_load_ndc_run(const crr_state_batch* in, const void* scratch, size_t scra
   if ((P.n_items || (P.n_tasks && P.n_incoming)) && !dst->items) return -1;
   if (P.n_tasks && (!tasks || !results || !routes || !out_items || !dst->branches || !dst->items || !dst->current)) return -1;
   if (P.n_tasks && P.n_incoming && !incoming) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   hipError_t e;
   if (in->n_wf) hipLaunchKernelGGL(load_branches_emit_kernel, grid_of(in->n_wf), dim3(kBlock), 0, s, c, k, *dst);
   else if ((e = hipMemsetAsync(dst->branch_begin, 0, sizeof(int64_t), s)) != hipSuccess) return (int)e;
@@ -967,9 +964,7 @@ int crr_load_store_checksums(const crr_state_batch* in, const void* scratch, siz
                   ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
     return -1;
   if (n_tasks && !result) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (n_tasks == 0) return 0;
   hipLaunchKernelGGL(load_store_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, a, after, result);
   return (int)hipGetLastError();
@@ -1004,9 +999,7 @@ int crr_load_store_vh_plan(const crr_state_batch* in, const void* scratch, size_
                            ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
     return -1;
   if (n_tasks && (!rows || !blob_off || !work || ((uintptr_t)work & 15u) || ((uintptr_t)blob_off & 7u))) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   const VhLayout L = carve_vh(n_tasks);
   memset(plan, 0, sizeof *plan);
   plan->n_tasks = n_tasks;
@@ -1026,10 +1019,8 @@ int crr_load_store_vh_plan(const crr_state_batch* in, const void* scratch, size_
   hipLaunchKernelGGL(load_store_vh_size_kernel, grid_of(n_tasks), dim3(kBlock), 0, s, c, a, after, rows, lens, marks);
   hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, lens, n_tasks, 1, totals);
   hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, marks, n_tasks, 1, totals + 1);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[2];
-  if ((e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, totals, h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   plan->n_bytes = h[0];
   plan->n_generated = h[1];
   return 0;
@@ -1057,9 +1048,7 @@ int crr_load_store_vh_run(const crr_state_batch* in, const void* scratch, size_t
   if (padded && (!out || ((uintptr_t)out & 15u))) return -1;
   const uint64_t n_chunks = padded / 16, blocks = (n_chunks + kBlock - 1) / kBlock;
   if (blocks > 0x7FFFFFFFull) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (n_chunks == 0) return 0;
   hipLaunchKernelGGL(load_store_vh_emit_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, c, a, after, blob_off,
                      plan_host->n_bytes, n_chunks, reinterpret_cast<ulonglong2*>(out));
@@ -1110,9 +1099,7 @@ int crr_load_mutation_plan(const crr_state_batch* in, const void* scratch, size_
                            ndc_plan_host, replay_in, replay_out, position, c, a, after) != 0)
     return -1;
   if (n_tasks && (!rows || !work || ((uintptr_t)work & 15u) || ((uintptr_t)rows & 3u))) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   const MutPlanLayout L = carve_mut_plan(n_tasks);
   memset(plan, 0, sizeof *plan);
   plan->n_tasks = n_tasks;
@@ -1128,10 +1115,8 @@ int crr_load_mutation_plan(const crr_state_batch* in, const void* scratch, size_
   hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, sums, L.n_blocks, kMutCols, totals);
   hipLaunchKernelGGL(load_mutation_offsets_kernel, dim3(L.n_blocks), dim3(kBlock), 0, s, rows, n_tasks, sums, L.n_blocks);
   hipError_t e;
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[kMutCols];
-  if ((e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, totals, h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   plan->n_exec = h[0];
   bool fits = true;
   for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
@@ -1174,9 +1159,7 @@ int crr_load_mutation_run(const crr_state_batch* in, const void* scratch, size_t
   }
   const MutRunLayout L = carve_mut_run(P);
   if (L.end > work_bytes || (L.end && (!work || ((uintptr_t)work & 15u)))) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (n_tasks == 0 || P.n_exec == 0) return 0;
   const void* tables[CRR_MUTATION_MAPS] = {replay_out->act, replay_out->timer, replay_out->child, replay_out->rc, replay_out->sig};
   MutDst d;
@@ -1241,13 +1224,8 @@ static int exec_setup(uint32_t n_tasks, const crr_inputs* replay_in, const crr_e
     const crr_blob_batch& B = *task_blobs;
     if (B.n_wf && !B.wf) return -1;
     if (B.n_blobs && (!B.bytes || !B.blob_off)) return -1;
-    if (B.n_wf && B.blob_off) {   // (a batch without offsets has no total to check against: it reads as absent)
-      x.tb_bytes = B.bytes;
-      x.tb_off = B.blob_off;
-      x.tb_wf = B.wf;
-      x.tb_n_blobs = B.n_blobs;
-      x.tb_n_wf = B.n_wf;
-    }
+    // (a batch without offsets has no total to check against: it reads as absent)
+    if (B.n_wf && B.blob_off) pack_task_blobs(x, B);
   }
   if (replay_in) {
     x.etype = replay_in->ev.etype;
@@ -1279,9 +1257,7 @@ int crr_load_store_exec_plan(const crr_state_batch* in, const void* scratch, siz
   if (exec_setup(n_tasks, replay_in, exec_tasks, vh_rows, vh_off, vh_plan_host, task_blobs, x) != 0) return -1;
   if (n_tasks && (!rows || !blob_off || !work || ((uintptr_t)work & 15u) || ((uintptr_t)blob_off & 7u) || ((uintptr_t)rows & 7u)))
     return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   const ExecLayout L = carve_exec(n_tasks);
   memset(plan, 0, sizeof *plan);
   plan->n_tasks = n_tasks;
@@ -1303,10 +1279,8 @@ int crr_load_store_exec_plan(const crr_state_batch* in, const void* scratch, siz
                      L.n_blocks);
   hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, sums, L.n_blocks, kExecCols, totals);
   hipLaunchKernelGGL(load_store_exec_offsets_kernel, dim3(L.n_blocks), dim3(kBlock), 0, s, rows, n_tasks, sums, blob_off);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[kExecCols];
-  if ((e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, totals, h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   plan->n_bytes = h[0];
   plan->n_blobs = h[1];
   plan->n_host = h[2];
@@ -1341,9 +1315,7 @@ int crr_load_store_exec_run(const crr_state_batch* in, const void* scratch, size
   if (x.vh_total && !vh_bytes) return -1;
   const uint64_t n_chunks = (n_bytes + 15) / 16, blocks = (n_chunks + kBlock - 1) / kBlock;
   if (n_chunks < n_bytes / 16 || blocks > 0x7FFFFFFFull) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (n_chunks == 0) return 0;
   const ExecScript* scripts = reinterpret_cast<const ExecScript*>(static_cast<const uint8_t*>(work) + L.scripts);
   hipLaunchKernelGGL(load_store_exec_emit_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, s, scripts, in->bytes,
@@ -1379,11 +1351,7 @@ static int resume_setup(const crr_state_batch* in, const void* scratch, size_t s
     const crr_blob_batch& B = *task_blobs;
     if (B.n_wf && !B.wf) return -1;
     if (!B.blob_off || (B.n_blobs && !B.bytes)) return -1;
-    r.tb_bytes = B.bytes;
-    r.tb_off = B.blob_off;
-    r.tb_wf = B.wf;
-    r.tb_n_blobs = B.n_blobs;
-    r.tb_n_wf = B.n_wf;
+    pack_task_blobs(r, B);
   }
   k.s = const_cast<uint8_t*>(static_cast<const uint8_t*>(work));
   k.L = carve_resume(in->n_wf);
@@ -1402,9 +1370,7 @@ int crr_load_resume_plan(const crr_state_batch* in, const void* scratch, size_t 
     return -1;
   if (n_tasks && (!routes || !rows || ((uintptr_t)rows & 3u))) return -1;
   if (in->n_wf && (!work || ((uintptr_t)work & 15u))) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   memset(plan, 0, sizeof *plan);
   plan->n_tasks = n_tasks;
   plan->n_wf = in->n_wf;
@@ -1427,10 +1393,8 @@ int crr_load_resume_plan(const crr_state_batch* in, const void* scratch, size_t 
   hipLaunchKernelGGL(load_resume_count_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, c, r, k);
   hipLaunchKernelGGL(load_ndc_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, k.sums(), k.L.n_blocks, kResCols, k.totals());
   hipLaunchKernelGGL(load_resume_offsets_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, k);
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[kResCols];
-  if ((e = hipMemcpyAsync(h, k.totals(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, k.totals(), h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   plan->n_applied = h[kResApplied];
   plan->n_blobs = h[kResBlobs];
   plan->blob_bytes = h[kResBlobBytes];
@@ -1473,9 +1437,7 @@ int crr_load_resume_gather(const crr_state_batch* in, const void* scratch, size_
   if (in->n_wf && (!out->wf || ((uintptr_t)out->wf & 7u) || !out->key_begin || !out->key_count || !out->task_of)) return -1;
   const uint64_t n_chunks = (P.n_bytes + 15) / 16, blocks = (n_chunks + kBlock - 1) / kBlock;
   if (n_chunks < P.n_bytes / 16 || blocks > 0x7FFFFFFFull) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   hipError_t e;
   if (in->n_wf == 0) return (int)hipMemsetAsync(out->blob_off, 0, sizeof(uint64_t), s);
   const ResumeTotals T = {P.n_blobs, P.blob_bytes, P.n_keys, P.key_bytes, P.n_bytes};
@@ -1503,9 +1465,7 @@ int crr_load_resume_finalize(const void* scratch, size_t scratch_bytes, const cr
     if (!plan_usable(scratch, scratch_bytes, summary_host, c)) return -1;
     if (!gathered_wf || !counts || count_stride < n_wf || !wf || ((uintptr_t)wf & 7u) || ((uintptr_t)gathered_wf & 7u)) return -1;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (n_wf == 0) {
     memset(totals, 0, sizeof *totals);
     return 0;
@@ -1519,10 +1479,8 @@ int crr_load_resume_finalize(const void* scratch, size_t scratch_bytes, const cr
   hipLaunchKernelGGL(load_resume_descriptor_kernel, dim3(k.L.n_blocks), dim3(kBlock), 0, s, c, k, gathered_wf, counts,
                      count_stride, wf, arena, (uint64_t)arena_capacity);
   hipError_t e;
-  if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   uint64_t h[kResCaps];
-  if ((e = hipMemcpyAsync(h, k.cap_totals(), sizeof h, hipMemcpyDeviceToHost, s)) != hipSuccess) return (int)e;
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
+  if ((e = read_totals(s, k.cap_totals(), h, sizeof h / sizeof h[0])) != hipSuccess) return (int)e;
   memset(totals, 0, sizeof *totals);
   totals->arena_bytes = P.token_bytes;
   for (int t = 0; t < kResCaps; ++t) totals->table_rows[t] = h[t];
@@ -1531,9 +1489,7 @@ int crr_load_resume_finalize(const void* scratch, size_t scratch_bytes, const cr
 
 int crr_load_resume_settle(const int32_t* task_of, crr_workflow* wf, uint32_t n_wf, void* stream) {
   if (n_wf && (!task_of || !wf || ((uintptr_t)task_of & 3u) || ((uintptr_t)wf & 7u))) return -1;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  crr_internal::StreamDevice on_dev_(s);
-  if (!on_dev_.ok) return (int)hipErrorInvalidHandle;
+  CRR_ON_STREAM(s, stream);
   if (n_wf == 0) return 0;
   hipLaunchKernelGGL(load_resume_settle_kernel, grid_of(n_wf), dim3(kBlock), 0, s, task_of, wf, n_wf);
   return (int)hipGetLastError();

@@ -9,8 +9,14 @@
 // crr_load_mutation_host (include/cadence_load_mutation.h) the same, then its count and emit passes and the gather;
 // crr_load_store_exec_host (include/cadence_load_store_exec.h) the same, then its decision and its splice per task;
 // crr_load_resume_host (include/cadence_load_resume.h) the load, then its decisions, serial prefixes and the gather.
+//
+// What the calls share is written once: Owned frees a scratch or work buffer, zeroed() gives every other temporary
+// an owner (so no exit path frees by hand, and out of memory is a NULL to test, never an exception), StoreHost is
+// the load, the branch walk and the branch table the four store-family calls start from, exclusive_scan every
+// serial prefix, write_vh_blobs the VersionHistories writer, load_decode.h's pack_task_blobs the tasks' event blobs.
 #include <stdlib.h>
 
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -40,20 +46,42 @@ void parallel_for(uint32_t n, int threads, Fn fn) {
   for (auto& th : pool) th.join();
 }
 
-void scan(const Ctx& c, int t) {
-  int64_t* p = c.cnt(t);
-  int64_t run = 0;
-  for (uint32_t w = 0; w < c.in.n_wf; ++w) {
-    const int64_t x = p[w];
-    p[w] = run;
+// p[0..n) to its exclusive prefix sums in place, p[n] = the total, which is returned
+template <class T>
+T exclusive_scan(T* p, uint32_t n) {
+  T run = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const T x = p[i];
+    p[i] = run;
     run += x;
   }
-  p[c.in.n_wf] = run;
+  p[n] = run;
+  return run;
 }
 
-// every phase of the load over a scratch this allocates (the caller frees c.s): 0, -1 invalid argument, -2 out of memory
-int run_load(const crr_state_batch* in, int threads, Ctx& c) {
-  c.s = nullptr;
+// a Ctx, NdcWork or ResumeWork whose buffer (.s) is this call's own
+template <class T>
+struct Owned : T {
+  Owned() { this->s = nullptr; }
+  ~Owned() { free(this->s); }
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+};
+
+struct Free {
+  void operator()(void* p) const { free(p); }
+};
+template <class T>
+using Buf = std::unique_ptr<T[], Free>;
+
+// n zeroed elements, or NULL when out of memory
+template <class T>
+Buf<T> zeroed(uint64_t n) {
+  return Buf<T>(static_cast<T*>(calloc((size_t)n, sizeof(T))));
+}
+
+// every phase of the load over a scratch this allocates (c owns it): 0, -1 invalid argument, -2 out of memory
+int run_load(const crr_state_batch* in, int threads, Owned<Ctx>& c) {
   if (in->n_blobs && (!in->bytes || !in->blob_off || !in->blob)) return -1;
   if (in->n_wf && !in->wf) return -1;
   const uint32_t n_wf = in->n_wf;
@@ -65,38 +93,33 @@ int run_load(const crr_state_batch* in, int threads, Ctx& c) {
   if (blobs != in->n_blobs) return -1;
   c.in = *in;
   c.L = carve(in->n_blobs, n_wf, nullptr);
-  uint8_t* fixed = static_cast<uint8_t*>(calloc(c.L.end + 16, 1));
-  if (!fixed) return -2;
-  c.s = fixed;
+  c.s = static_cast<uint8_t*>(calloc(c.L.end + 16, 1));
+  if (!c.s) return -2;
   c.err()[0] = ~0ull;
   parallel_for(in->n_blobs, threads, [&](uint32_t b, Frame* stk) { parse_blob(c, b, stk); });
   parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { count_wf(c, w, stk); });
   for (int t = 0; t < kCounters; ++t)
-    if (t != CRR_LOAD_T_KEYS && t != CRR_LOAD_T_KEY_BYTES) scan(c, t);
+    if (t != CRR_LOAD_T_KEYS && t != CRR_LOAD_T_KEY_BYTES) exclusive_scan(c.cnt(t), n_wf);
   uint64_t tot[kCounters];
   for (int t = 0; t < kCounters; ++t) tot[t] = (uint64_t)c.cnt(t)[n_wf];
   const Layout full = carve(in->n_blobs, n_wf, tot);
-  uint8_t* s = static_cast<uint8_t*>(realloc(fixed, full.end + 16));
-  if (!s) {
-    free(fixed);
-    c.s = nullptr;
-    return -2;
-  }
+  uint8_t* s = static_cast<uint8_t*>(realloc(c.s, full.end + 16));
+  if (!s) return -2;
   memset(s + c.L.end, 0, full.end + 16 - c.L.end);
   c.s = s;
   c.L = full;
   parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { emit_wf(c, w, stk); });
-  scan(c, CRR_LOAD_T_KEYS);
-  scan(c, CRR_LOAD_T_KEY_BYTES);
+  exclusive_scan(c.cnt(CRR_LOAD_T_KEYS), n_wf);
+  exclusive_scan(c.cnt(CRR_LOAD_T_KEY_BYTES), n_wf);
   parallel_for(n_wf, threads, [&](uint32_t w, Frame*) { dict_wf(c, w); });
   return 0;
 }
 
 constexpr CrcTab kCrcTab = make_crc_tab();
 
-// the branch walk's count phase and its serial scans over a work buffer this allocates (the caller frees k.s):
+// the branch walk's count phase and its serial scans over a work buffer this allocates (k owns it):
 // 0, -2 out of memory
-int count_branches(const Ctx& c, int threads, NdcWork& k) {
+int count_branches(const Ctx& c, int threads, Owned<NdcWork>& k) {
   const uint32_t n_wf = c.in.n_wf;
   k.L = carve_ndc(n_wf, 0);
   k.n_wf = n_wf;
@@ -104,17 +127,63 @@ int count_branches(const Ctx& c, int threads, NdcWork& k) {
   k.s = static_cast<uint8_t*>(calloc(k.L.end + 16, 1));
   if (!k.s) return -2;
   parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_count_wf(c, k, w, stk); });
-  for (int t = 0; t < 2; ++t) {
-    int64_t* p = k.cnt(t);
-    int64_t run = 0;
-    for (uint32_t w = 0; w < n_wf; ++w) {
-      const int64_t x = p[w];
-      p[w] = run;
-      run += x;
-    }
-    p[n_wf] = run;
-  }
+  for (int t = 0; t < 2; ++t) exclusive_scan(k.cnt(t), n_wf);
   return 0;
+}
+
+// what the four store-family calls start from: the load, the branch walk into a table of this call, and the tasks
+// with their decisions over it (a) beside the dense after-image (img).  rc: 0, -1 invalid argument, -2 out of memory
+struct StoreHost {
+  Owned<Ctx> c;
+  Owned<NdcWork> k;
+  StoreIn a;
+  ImageAfter img;
+  Buf<crr_ndc_branch> branches;
+  Buf<crr_vh_item> items;
+  Buf<crr_branch_token> tokens;
+  Buf<int64_t> branch_begin;
+  Buf<int32_t> current;
+  int rc;
+
+  StoreHost(const crr_state_batch* in, const crr_repl_task* tasks, const crr_last_event* last_events, uint32_t n_tasks,
+            const crr_ndc_result* results, const crr_ndc_route* routes, const crr_load_image* after, int threads)
+      : img{after, in->n_wf} {
+    rc = run_load(in, threads, c);
+    if (rc != 0) return;
+    rc = -2;
+    if (count_branches(c, threads, k) != 0) return;
+    const uint32_t n_wf = in->n_wf;
+    a.tasks = tasks;
+    a.last = last_events;
+    a.results = results;
+    a.routes = routes;
+    a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
+    a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
+    a.n_tasks = n_tasks;
+    // (calloc(0) may be NULL: at least one element each)
+    a.br.branches = (branches = zeroed<crr_ndc_branch>(a.n_branches + 1)).get();
+    a.br.items = (items = zeroed<crr_vh_item>(a.n_items + 1)).get();
+    a.br.tokens = (tokens = zeroed<crr_branch_token>(a.n_branches + 1)).get();
+    a.br.branch_begin = (branch_begin = zeroed<int64_t>((uint64_t)n_wf + 1)).get();
+    a.br.current = (current = zeroed<int32_t>((uint64_t)n_wf + 1)).get();
+    if (!branches || !items || !tokens || !branch_begin || !current) return;
+    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
+    rc = 0;
+  }
+};
+
+// the VersionHistories blob of every generated task at dst + off[i], by load_decode.h's sequential writer; a task
+// whose blob does not come out at its planned length is left as zeros
+void write_vh_blobs(const Ctx& c, const StoreIn& a, const ImageAfter& img, const uint64_t* off, uint8_t* dst,
+                    uint32_t n_tasks, int threads) {
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) {
+    const uint64_t len = off[i + 1] - off[i];
+    if (len == 0) return;
+    StoreDecision D;
+    store_decide(c, a, img, i, D);
+    ByteSink K = {dst + off[i], len, 0};
+    if (!D.generated() || !vh_blob_write(K, c, a, D) || K.len != len) memset(dst + off[i], 0, (size_t)len);
+  });
 }
 
 }  // namespace
@@ -122,7 +191,7 @@ int count_branches(const Ctx& c, int threads, NdcWork& k) {
 extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_image* dst, crr_load_summary* summary,
                                     int threads) {
   if (!in || !summary) return -1;
-  Ctx c;
+  Owned<Ctx> c;
   const int rc = run_load(in, threads, c);
   if (rc != 0) return rc;
   const uint32_t n_wf = in->n_wf;
@@ -142,7 +211,6 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
     if (dst->status) memcpy(dst->status, c.status(), n * sizeof(int32_t));
     if (dst->flags) memcpy(dst->flags, c.flags(), n * sizeof(uint32_t));
   }
-  free(c.s);
   return 0;
 }
 
@@ -151,15 +219,12 @@ extern "C" int crr_load_states_host(const crr_state_batch* in, const crr_load_im
 extern "C" int crr_load_branches_host(const crr_state_batch* in, const crr_load_branches* dst, crr_load_ndc_sizes* plan,
                                       int threads) {
   if (!in || !plan) return -1;
-  Ctx c;
+  Owned<Ctx> c;
   const int rc = run_load(in, threads, c);
   if (rc != 0) return rc;
   const uint32_t n_wf = in->n_wf;
-  NdcWork k;
-  if (count_branches(c, threads, k) != 0) {
-    free(c.s);
-    return -2;
-  }
+  Owned<NdcWork> k;
+  if (count_branches(c, threads, k) != 0) return -2;
   memset(plan, 0, sizeof *plan);
   plan->n_wf = n_wf;
   plan->n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
@@ -169,8 +234,6 @@ extern "C" int crr_load_branches_host(const crr_state_batch* in, const crr_load_
     parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, *dst, stk); });
     if (n_wf == 0 && dst->branch_begin) dst->branch_begin[0] = 0;
   }
-  free(k.s);
-  free(c.s);
   return 0;
 }
 
@@ -182,39 +245,10 @@ extern "C" int crr_load_store_checksums_host(const crr_state_batch* in, const cr
                                              const crr_load_image* after, crr_store_row* result, int threads) {
   if (!in || (n_tasks && (!tasks || !last_events || !results || !routes || !result))) return -1;
   if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
-  Ctx c;
-  const int rc = run_load(in, threads, c);
-  if (rc != 0) return rc;
-  const uint32_t n_wf = in->n_wf;
-  NdcWork k;
-  if (count_branches(c, threads, k) != 0) {
-    free(c.s);
-    return -2;
-  }
-  StoreIn a;
-  a.tasks = tasks;
-  a.last = last_events;
-  a.results = results;
-  a.routes = routes;
-  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
-  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
-  a.n_tasks = n_tasks;
-  // one block for the table (calloc(0) may be NULL: at least one element each)
-  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
-  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
-  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
-  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
-  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
-  const bool ok = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current;
-  if (ok) {
-    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
-    const ImageAfter img = {after, n_wf};
-    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { store_task(c, a, img, kCrcTab.v, i, result); });
-  }
-  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
-  free(k.s);
-  free(c.s);
-  return ok ? 0 : -2;
+  StoreHost h(in, tasks, last_events, n_tasks, results, routes, after, threads);
+  if (h.rc != 0) return h.rc;
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { store_task(h.c, h.a, h.img, kCrcTab.v, i, result); });
+  return 0;
 }
 
 // the VersionHistories blob to store for routed tasks (include/cadence_load_store_vh.h): the same load, branch walk
@@ -226,71 +260,30 @@ extern "C" int crr_load_store_vh_host(const crr_state_batch* in, const crr_repl_
                                       int threads) {
   if (!in || !plan || (n_tasks && (!tasks || !last_events || !results || !routes))) return -1;
   if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
-  Ctx c;
-  const int rc = run_load(in, threads, c);
-  if (rc != 0) return rc;
-  const uint32_t n_wf = in->n_wf;
-  NdcWork k;
-  if (count_branches(c, threads, k) != 0) {
-    free(c.s);
-    return -2;
+  StoreHost h(in, tasks, last_events, n_tasks, results, routes, after, threads);
+  if (h.rc != 0) return h.rc;
+  const Buf<crr_vh_blob_row> row_buf = zeroed<crr_vh_blob_row>((uint64_t)n_tasks + 1);
+  const Buf<uint64_t> off_buf = zeroed<uint64_t>((uint64_t)n_tasks + 1);
+  if (!row_buf || !off_buf) return -2;
+  crr_vh_blob_row* my_rows = row_buf.get();
+  uint64_t* my_off = off_buf.get();
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { my_off[i] = vh_size_task(h.c, h.a, h.img, i, my_rows); });
+  uint64_t generated = 0;
+  for (uint32_t i = 0; i < n_tasks; ++i) generated += my_off[i] != 0;
+  const uint64_t run = exclusive_scan(my_off, n_tasks);
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  plan->n_generated = generated;
+  plan->n_bytes = run;
+  const uint64_t padded = align16(run);
+  if (out && (uint64_t)out_capacity < padded) return -1;   // nothing written
+  if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_vh_blob_row));
+  if (blob_off) memcpy(blob_off, my_off, ((size_t)n_tasks + 1) * sizeof(uint64_t));
+  if (out) {
+    write_vh_blobs(h.c, h.a, h.img, my_off, out, n_tasks, threads);
+    if (padded > run) memset(out + run, 0, (size_t)(padded - run));
   }
-  StoreIn a;
-  a.tasks = tasks;
-  a.last = last_events;
-  a.results = results;
-  a.routes = routes;
-  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
-  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
-  a.n_tasks = n_tasks;
-  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
-  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
-  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
-  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
-  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
-  crr_vh_blob_row* my_rows = static_cast<crr_vh_blob_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_vh_blob_row)));
-  uint64_t* my_off = static_cast<uint64_t*>(calloc((size_t)n_tasks + 1, sizeof(uint64_t)));
-  int ret = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current && my_rows && my_off ? 0 : -2;
-  if (ret == 0) {
-    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
-    const ImageAfter img = {after, n_wf};
-    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { my_off[i] = vh_size_task(c, a, img, i, my_rows); });
-    uint64_t run = 0, generated = 0;
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-      const uint64_t len = my_off[i];
-      my_off[i] = run;
-      run += len;
-      generated += len != 0;
-    }
-    my_off[n_tasks] = run;
-    memset(plan, 0, sizeof *plan);
-    plan->n_tasks = n_tasks;
-    plan->n_generated = generated;
-    plan->n_bytes = run;
-    const uint64_t padded = align16(run);
-    if (out && (uint64_t)out_capacity < padded) {
-      ret = -1;   // nothing written
-    } else {
-      if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_vh_blob_row));
-      if (blob_off) memcpy(blob_off, my_off, ((size_t)n_tasks + 1) * sizeof(uint64_t));
-      if (out) {
-        parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) {
-          const uint64_t len = my_off[i + 1] - my_off[i];
-          if (len == 0) return;
-          StoreDecision D;
-          store_decide(c, a, img, i, D);
-          ByteSink K = {out + my_off[i], len, 0};
-          if (!D.generated() || !vh_blob_write(K, c, a, D) || K.len != len) memset(out + my_off[i], 0, (size_t)len);
-        });
-        if (padded > run) memset(out + run, 0, (size_t)(padded - run));
-      }
-    }
-  }
-  free(my_rows), free(my_off);
-  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
-  free(k.s);
-  free(c.s);
-  return ret;
+  return 0;
 }
 
 // the pending-entry mutation to store for routed tasks (include/cadence_load_mutation.h): the same load, branch walk
@@ -302,100 +295,69 @@ extern "C" int crr_load_mutation_host(const crr_state_batch* in, const crr_repl_
                                       const crr_mutation_out* out, crr_mutation_sizes* plan, int threads) {
   if (!in || !plan || (n_tasks && (!tasks || !last_events || !results || !routes))) return -1;
   if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
-  Ctx c;
-  const int rc = run_load(in, threads, c);
-  if (rc != 0) return rc;
-  const uint32_t n_wf = in->n_wf;
-  NdcWork k;
-  if (count_branches(c, threads, k) != 0) {
-    free(c.s);
-    return -2;
-  }
-  StoreIn a;
-  a.tasks = tasks;
-  a.last = last_events;
-  a.results = results;
-  a.routes = routes;
-  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
-  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
-  a.n_tasks = n_tasks;
-  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
-  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
-  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
-  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
-  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
-  crr_mutation_row* my_rows = static_cast<crr_mutation_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_mutation_row)));
-  uint64_t* dir[1 + CRR_MUTATION_MAPS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int ret = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current && my_rows ? 0 : -2;
-  if (ret == 0) {
-    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
-    const ImageAfter img = {after, n_wf};
-    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { mutation_count_task(c, a, img, i, my_rows[i]); });
-    memset(plan, 0, sizeof *plan);
-    plan->n_tasks = n_tasks;
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-      crr_mutation_row& o = my_rows[i];
-      if (o.exec_index != 0xFFFFFFFFu) o.exec_index = (uint32_t)plan->n_exec++;
-      for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
-        o.map[t].upsert_begin = (uint32_t)plan->n_upsert[t];
-        o.map[t].delete_begin = (uint32_t)plan->n_delete[t];
-        plan->n_upsert[t] += o.map[t].n_upsert;
-        plan->n_delete[t] += o.map[t].n_delete;
-      }
-    }
-    uint64_t dir_bytes = align16(plan->n_exec * sizeof(uint64_t));
+  StoreHost h(in, tasks, last_events, n_tasks, results, routes, after, threads);
+  if (h.rc != 0) return h.rc;
+  const Buf<crr_mutation_row> row_buf = zeroed<crr_mutation_row>((uint64_t)n_tasks + 1);
+  if (!row_buf) return -2;
+  crr_mutation_row* my_rows = row_buf.get();
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { mutation_count_task(h.c, h.a, h.img, i, my_rows[i]); });
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  for (uint32_t i = 0; i < n_tasks; ++i) {
+    crr_mutation_row& o = my_rows[i];
+    if (o.exec_index != 0xFFFFFFFFu) o.exec_index = (uint32_t)plan->n_exec++;
     for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
-      dir_bytes += align16(plan->n_upsert[t] * sizeof(uint64_t));
-      if (plan->n_upsert[t] > 0xFFFFFFFFull || plan->n_delete[t] > 0xFFFFFFFFull) ret = -1;
-    }
-    plan->run_work_needed = dir_bytes;
-    if (out && ret == 0) {
-      auto usable = [](const void* p, uint64_t capacity, uint64_t total) { return capacity >= total && (total == 0 || p); };
-      bool ok = usable(out->exec, out->exec_capacity, plan->n_exec);
-      for (int t = 0; t < CRR_MUTATION_MAPS; ++t)
-        ok = ok && usable(out->upsert[t], out->upsert_capacity[t], plan->n_upsert[t]) &&
-             usable(out->deleted[t], out->delete_capacity[t], plan->n_delete[t]);
-      if (!ok) ret = -1;   // nothing written
-    }
-    if (ret == 0 && rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_mutation_row));
-    if (ret == 0 && out && plan->n_exec) {
-      MutDst d;
-      memset(&d, 0, sizeof d);
-      d.n_exec = plan->n_exec;
-      dir[0] = static_cast<uint64_t*>(malloc((size_t)plan->n_exec * sizeof(uint64_t)));
-      bool ok = dir[0] != nullptr;
-      for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
-        dir[1 + t] = static_cast<uint64_t*>(malloc(((size_t)plan->n_upsert[t] + 1) * sizeof(uint64_t)));
-        ok = ok && dir[1 + t];
-        d.dir[t] = dir[1 + t];
-        d.keys[t] = out->deleted[t];
-        d.base[t] = static_cast<const uint8_t*>(after->rows[t]);
-        d.n_upsert[t] = plan->n_upsert[t];
-        d.n_delete[t] = plan->n_delete[t];
-      }
-      d.dir_exec = dir[0];
-      if (!ok) {
-        ret = -2;
-      } else {
-        memset(dir[0], 0xFF, (size_t)plan->n_exec * sizeof(uint64_t));
-        for (int t = 0; t < CRR_MUTATION_MAPS; ++t) memset(dir[1 + t], 0xFF, (size_t)plan->n_upsert[t] * sizeof(uint64_t));
-        parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { mutation_emit_task(c, a, img, i, my_rows, d); });
-        auto gather = [&](const void* table, const uint64_t* dr, uint32_t row_bytes, uint64_t n_rows, void* dst) {
-          const uint32_t words = row_bytes / 8;
-          uint64_t* q = static_cast<uint64_t*>(dst);
-          for (uint64_t g = 0; g < n_rows * words; ++g) q[g] = mutation_gather_word(static_cast<const uint64_t*>(table), dr, words, g);
-        };
-        gather(after->exec, d.dir_exec, sizeof(crr_exec_row), plan->n_exec, out->exec);
-        for (int t = 0; t < CRR_MUTATION_MAPS; ++t) gather(after->rows[t], d.dir[t], kRowBytes[t], plan->n_upsert[t], out->upsert[t]);
-      }
+      o.map[t].upsert_begin = (uint32_t)plan->n_upsert[t];
+      o.map[t].delete_begin = (uint32_t)plan->n_delete[t];
+      plan->n_upsert[t] += o.map[t].n_upsert;
+      plan->n_delete[t] += o.map[t].n_delete;
     }
   }
-  for (uint64_t* p : dir) free(p);
-  free(my_rows);
-  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
-  free(k.s);
-  free(c.s);
-  return ret;
+  bool ok = true;
+  uint64_t dir_bytes = align16(plan->n_exec * sizeof(uint64_t));
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+    dir_bytes += align16(plan->n_upsert[t] * sizeof(uint64_t));
+    if (plan->n_upsert[t] > 0xFFFFFFFFull || plan->n_delete[t] > 0xFFFFFFFFull) ok = false;
+  }
+  plan->run_work_needed = dir_bytes;
+  if (out && ok) {
+    auto usable = [](const void* p, uint64_t capacity, uint64_t total) { return capacity >= total && (total == 0 || p); };
+    ok = usable(out->exec, out->exec_capacity, plan->n_exec);
+    for (int t = 0; t < CRR_MUTATION_MAPS; ++t)
+      ok = ok && usable(out->upsert[t], out->upsert_capacity[t], plan->n_upsert[t]) &&
+           usable(out->deleted[t], out->delete_capacity[t], plan->n_delete[t]);
+  }
+  if (!ok) return -1;   // nothing written
+  if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_mutation_row));
+  if (!out || !plan->n_exec) return 0;
+  MutDst d;
+  memset(&d, 0, sizeof d);
+  d.n_exec = plan->n_exec;
+  const Buf<uint64_t> dir_exec = zeroed<uint64_t>(plan->n_exec);
+  Buf<uint64_t> dir[CRR_MUTATION_MAPS];
+  ok = dir_exec != nullptr;
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) {
+    dir[t] = zeroed<uint64_t>(plan->n_upsert[t] + 1);
+    ok = ok && dir[t];
+    d.dir[t] = dir[t].get();
+    d.keys[t] = out->deleted[t];
+    d.base[t] = static_cast<const uint8_t*>(after->rows[t]);
+    d.n_upsert[t] = plan->n_upsert[t];
+    d.n_delete[t] = plan->n_delete[t];
+  }
+  d.dir_exec = dir_exec.get();
+  if (!ok) return -2;
+  memset(d.dir_exec, 0xFF, (size_t)plan->n_exec * sizeof(uint64_t));
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) memset(d.dir[t], 0xFF, (size_t)plan->n_upsert[t] * sizeof(uint64_t));
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { mutation_emit_task(h.c, h.a, h.img, i, my_rows, d); });
+  auto gather = [&](const void* table, const uint64_t* dr, uint32_t row_bytes, uint64_t n_rows, void* dst) {
+    const uint32_t words = row_bytes / 8;
+    uint64_t* q = static_cast<uint64_t*>(dst);
+    for (uint64_t g = 0; g < n_rows * words; ++g) q[g] = mutation_gather_word(static_cast<const uint64_t*>(table), dr, words, g);
+  };
+  gather(after->exec, d.dir_exec, sizeof(crr_exec_row), plan->n_exec, out->exec);
+  for (int t = 0; t < CRR_MUTATION_MAPS; ++t) gather(after->rows[t], d.dir[t], kRowBytes[t], plan->n_upsert[t], out->upsert[t]);
+  return 0;
 }
 
 // the execution blob to store for routed tasks (include/cadence_load_store_exec.h): the same load, branch walk and
@@ -412,114 +374,60 @@ extern "C" int crr_load_store_exec_host(const crr_state_batch* in, const crr_rep
   if (after && in->n_wf && (!after->exec || !after->offsets)) return -1;
   if (task_blobs && ((task_blobs->n_wf && !task_blobs->wf) || (task_blobs->n_blobs && (!task_blobs->bytes || !task_blobs->blob_off))))
     return -1;
-  Ctx c;
-  const int rc = run_load(in, threads, c);
-  if (rc != 0) return rc;
-  const uint32_t n_wf = in->n_wf;
-  NdcWork k;
-  if (count_branches(c, threads, k) != 0) {
-    free(c.s);
-    return -2;
+  StoreHost h(in, tasks, last_events, n_tasks, results, routes, after, threads);
+  if (h.rc != 0) return h.rc;
+  const Buf<crr_vh_blob_row> vh_row_buf = zeroed<crr_vh_blob_row>((uint64_t)n_tasks + 1);
+  const Buf<uint64_t> vh_off_buf = zeroed<uint64_t>((uint64_t)n_tasks + 1);
+  const Buf<crr_exec_blob_row> row_buf = zeroed<crr_exec_blob_row>((uint64_t)n_tasks + 1);
+  const Buf<uint64_t> off_buf = zeroed<uint64_t>((uint64_t)n_tasks + 1);
+  if (!vh_row_buf || !vh_off_buf || !row_buf || !off_buf) return -2;
+  crr_vh_blob_row* vh_rows = vh_row_buf.get();
+  uint64_t* vh_off = vh_off_buf.get();
+  crr_exec_blob_row* my_rows = row_buf.get();
+  uint64_t* my_off = off_buf.get();
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { vh_off[i] = vh_size_task(h.c, h.a, h.img, i, vh_rows); });
+  const Buf<uint8_t> vh_buf = zeroed<uint8_t>(exclusive_scan(vh_off, n_tasks) + 1);
+  if (!vh_buf) return -2;
+  uint8_t* vh_bytes = vh_buf.get();
+  write_vh_blobs(h.c, h.a, h.img, vh_off, vh_bytes, n_tasks, threads);
+  ExecIn x;
+  memset(&x, 0, sizeof x);
+  x.xt = exec_tasks;
+  x.vh_rows = vh_rows;
+  x.vh_off = vh_off;
+  x.vh_total = vh_off[n_tasks];
+  if (task_blobs && task_blobs->n_wf && task_blobs->blob_off) pack_task_blobs(x, *task_blobs);
+  x.upserts = upserts;
+  parallel_for(n_tasks, threads, [&](uint32_t i, Frame* stk) {
+    ExecScript S;
+    bool vh_bad;
+    my_off[i] = exec_size_task(h.c, h.a, h.img, x, i, my_rows, &S, vh_bad, stk);
+  });
+  memset(plan, 0, sizeof *plan);
+  plan->n_tasks = n_tasks;
+  for (uint32_t i = 0; i < n_tasks; ++i) {
+    plan->n_blobs += my_off[i] != 0;
+    plan->n_host += my_off[i] == 0 && my_rows[i].flags != 0;
   }
-  StoreIn a;
-  a.tasks = tasks;
-  a.last = last_events;
-  a.results = results;
-  a.routes = routes;
-  a.n_branches = (uint64_t)k.cnt(kBrHist)[n_wf];
-  a.n_items = (uint64_t)k.cnt(kBrItems)[n_wf];
-  a.n_tasks = n_tasks;
-  a.br.branches = static_cast<crr_ndc_branch*>(calloc(a.n_branches + 1, sizeof(crr_ndc_branch)));
-  a.br.items = static_cast<crr_vh_item*>(calloc(a.n_items + 1, sizeof(crr_vh_item)));
-  a.br.tokens = static_cast<crr_branch_token*>(calloc(a.n_branches + 1, sizeof(crr_branch_token)));
-  a.br.branch_begin = static_cast<int64_t*>(calloc((size_t)n_wf + 1, sizeof(int64_t)));
-  a.br.current = static_cast<int32_t*>(calloc((size_t)n_wf + 1, sizeof(int32_t)));
-  crr_vh_blob_row* vh_rows = static_cast<crr_vh_blob_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_vh_blob_row)));
-  uint64_t* vh_off = static_cast<uint64_t*>(calloc((size_t)n_tasks + 1, sizeof(uint64_t)));
-  crr_exec_blob_row* my_rows = static_cast<crr_exec_blob_row*>(calloc((size_t)n_tasks + 1, sizeof(crr_exec_blob_row)));
-  uint64_t* my_off = static_cast<uint64_t*>(calloc((size_t)n_tasks + 1, sizeof(uint64_t)));
-  uint8_t* vh_bytes = nullptr;
-  int ret = a.br.branches && a.br.items && a.br.tokens && a.br.branch_begin && a.br.current && vh_rows && vh_off && my_rows && my_off ? 0 : -2;
-  if (ret == 0) {
-    parallel_for(n_wf, threads, [&](uint32_t w, Frame* stk) { branches_emit_wf(c, k, w, a.br, stk); });
-    const ImageAfter img = {after, n_wf};
-    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) { vh_off[i] = vh_size_task(c, a, img, i, vh_rows); });
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-      const uint64_t len = vh_off[i];
-      vh_off[i] = run;
-      run += len;
-    }
-    vh_off[n_tasks] = run;
-    vh_bytes = static_cast<uint8_t*>(calloc((size_t)run + 1, 1));
-    if (!vh_bytes) ret = -2;
-  }
-  if (ret == 0) {
-    const ImageAfter img = {after, n_wf};
-    parallel_for(n_tasks, threads, [&](uint32_t i, Frame*) {
-      const uint64_t len = vh_off[i + 1] - vh_off[i];
-      if (len == 0) return;
-      StoreDecision D;
-      store_decide(c, a, img, i, D);
-      ByteSink K = {vh_bytes + vh_off[i], len, 0};
-      if (!D.generated() || !vh_blob_write(K, c, a, D) || K.len != len) memset(vh_bytes + vh_off[i], 0, (size_t)len);
-    });
-    ExecIn x;
-    memset(&x, 0, sizeof x);
-    x.xt = exec_tasks;
-    x.vh_rows = vh_rows;
-    x.vh_off = vh_off;
-    x.vh_total = vh_off[n_tasks];
-    if (task_blobs && task_blobs->n_wf && task_blobs->blob_off) {
-      x.tb_bytes = task_blobs->bytes;
-      x.tb_off = task_blobs->blob_off;
-      x.tb_wf = task_blobs->wf;
-      x.tb_n_blobs = task_blobs->n_blobs;
-      x.tb_n_wf = task_blobs->n_wf;
-    }
-    x.upserts = upserts;
+  const uint64_t run = exclusive_scan(my_off, n_tasks);
+  plan->n_bytes = run;
+  if (out && (uint64_t)out_capacity < run) return -1;   // nothing written
+  if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_exec_blob_row));
+  if (blob_off) memcpy(blob_off, my_off, ((size_t)n_tasks + 1) * sizeof(uint64_t));
+  if (out) {
     parallel_for(n_tasks, threads, [&](uint32_t i, Frame* stk) {
-      ExecScript S;
+      const uint64_t len = my_off[i + 1] - my_off[i];
+      if (len == 0) return;
+      crr_exec_blob_row row;
+      StoreDecision D;
+      ExecTask T;
       bool vh_bad;
-      my_off[i] = exec_size_task(c, a, img, x, i, my_rows, &S, vh_bad, stk);
+      ExecSinkEm em = {{out + my_off[i], len, 0}, in->bytes, vh_bytes, x.tb_bytes};
+      if (!exec_plan_task(h.c, h.a, h.img, x, i, row, D, T, vh_bad, stk) || !exec_walk(h.c, D.S.R, T, em, stk) || em.K.len != len)
+        memset(out + my_off[i], 0, (size_t)len);
     });
-    memset(plan, 0, sizeof *plan);
-    plan->n_tasks = n_tasks;
-    uint64_t run = 0;
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-      const uint64_t len = my_off[i];
-      my_off[i] = run;
-      run += len;
-      plan->n_blobs += len != 0;
-      plan->n_host += len == 0 && my_rows[i].flags != 0;
-    }
-    my_off[n_tasks] = run;
-    plan->n_bytes = run;
-    if (out && (uint64_t)out_capacity < run) {
-      ret = -1;   // nothing written
-    } else {
-      if (rows && n_tasks) memcpy(rows, my_rows, (size_t)n_tasks * sizeof(crr_exec_blob_row));
-      if (blob_off) memcpy(blob_off, my_off, ((size_t)n_tasks + 1) * sizeof(uint64_t));
-      if (out) {
-        parallel_for(n_tasks, threads, [&](uint32_t i, Frame* stk) {
-          const uint64_t len = my_off[i + 1] - my_off[i];
-          if (len == 0) return;
-          crr_exec_blob_row row;
-          StoreDecision D;
-          ExecTask T;
-          bool vh_bad;
-          ExecSinkEm em = {{out + my_off[i], len, 0}, in->bytes, vh_bytes, x.tb_bytes};
-          if (!exec_plan_task(c, a, img, x, i, row, D, T, vh_bad, stk) || !exec_walk(c, D.S.R, T, em, stk) || em.K.len != len)
-            memset(out + my_off[i], 0, (size_t)len);
-        });
-      }
-    }
   }
-  free(vh_bytes), free(vh_rows), free(vh_off), free(my_rows), free(my_off);
-  free(a.br.branches), free(a.br.items), free(a.br.tokens), free(a.br.branch_begin), free(a.br.current);
-  free(k.s);
-  free(c.s);
-  return ret;
+  return 0;
 }
 
 // the resumed replay of routed tasks planned from the loaded states (include/cadence_load_resume.h): the same load,
@@ -533,7 +441,7 @@ extern "C" int crr_load_resume_host(const crr_state_batch* in, const crr_repl_ta
   if (!in || !plan || (n_tasks && (!tasks || !routes || !task_blobs))) return -1;
   if (task_blobs && ((task_blobs->n_wf && !task_blobs->wf) || !task_blobs->blob_off || (task_blobs->n_blobs && !task_blobs->bytes)))
     return -1;
-  Ctx c;
+  Owned<Ctx> c;
   const int rc = run_load(in, threads, c);
   if (rc != 0) return rc;
   const uint32_t n_wf = in->n_wf;
@@ -542,21 +450,12 @@ extern "C" int crr_load_resume_host(const crr_state_batch* in, const crr_repl_ta
   r.tasks = tasks;
   r.routes = routes;
   r.n_tasks = n_tasks;
-  if (task_blobs) {
-    r.tb_bytes = task_blobs->bytes;
-    r.tb_off = task_blobs->blob_off;
-    r.tb_wf = task_blobs->wf;
-    r.tb_n_blobs = task_blobs->n_blobs;
-    r.tb_n_wf = task_blobs->n_wf;
-  }
-  ResumeWork k;
+  if (task_blobs) pack_task_blobs(r, *task_blobs);
+  Owned<ResumeWork> k;
   k.L = carve_resume(n_wf);
   k.n_wf = n_wf;
   k.s = static_cast<uint8_t*>(calloc(k.L.end + 16, 1));
-  if (!k.s) {
-    free(c.s);
-    return -2;
-  }
+  if (!k.s) return -2;
   int ret = 0;
   memset(k.winner(), 0xFF, (size_t)n_wf * sizeof(uint32_t));
   for (uint32_t i = n_tasks; i-- > 0;)   // descending: the lowest index is written last
@@ -595,10 +494,11 @@ extern "C" int crr_load_resume_host(const crr_state_batch* in, const crr_repl_ta
     if (!ok) ret = -1;   // nothing written
   }
   if (ret == 0 && (wf || arena) && (uint64_t)arena_capacity < plan->token_bytes) ret = -1;
-  if (ret == 0 && rows)
+  if (ret != 0) return ret;
+  if (rows)
     for (uint32_t i = 0; i < n_tasks; ++i) rows[i] = resume_row(c, r, k.winner(), i);
   const ResumeTotals T = {plan->n_blobs, plan->blob_bytes, plan->n_keys, plan->key_bytes, plan->n_bytes};
-  if (ret == 0 && out) {
+  if (out) {
     for (uint32_t p = 0; p < n_wf; ++p) {
       out->wf[p] = resume_blob_wf(r, k, p);
       out->key_begin[p] = (uint32_t)k.off(kResKeys)[p];
@@ -616,35 +516,29 @@ extern "C" int crr_load_resume_host(const crr_state_batch* in, const crr_repl_ta
       for (uint64_t b = 0; b < n; ++b) out->bytes[16 * i + b] = (uint8_t)((b < 8 ? lo >> (8 * b) : hi >> (8 * (b - 8))) & 0xffu);
     }
   }
-  if (ret == 0 && counts && wf && out && n_wf) {
-    if (plan->token_bytes && !arena) {
-      ret = -1;
-    } else {
-      uint64_t base[kResCaps] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (uint32_t p = 0; p < n_wf; ++p) {
-        uint64_t cap[kResCaps];
-        resume_caps(c, k, counts, n_wf, p, cap);
-        wf[p] = resume_descriptor(c, k, out->wf, counts, n_wf, p, cap, base, arena, arena_capacity);
-        for (int t = 0; t < kResCaps; ++t) base[t] += cap[t];
-      }
-      if (totals)
-        for (int t = 0; t < kResCaps; ++t) totals->table_rows[t] = base[t];
+  if (counts && wf && out && n_wf) {
+    if (plan->token_bytes && !arena) return -1;
+    uint64_t base[kResCaps] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint32_t p = 0; p < n_wf; ++p) {
+      uint64_t cap[kResCaps];
+      resume_caps(c, k, counts, n_wf, p, cap);
+      wf[p] = resume_descriptor(c, k, out->wf, counts, n_wf, p, cap, base, arena, arena_capacity);
+      for (int t = 0; t < kResCaps; ++t) base[t] += cap[t];
     }
+    if (totals)
+      for (int t = 0; t < kResCaps; ++t) totals->table_rows[t] = base[t];
   }
-  free(k.s);
-  free(c.s);
-  return ret;
+  return 0;
 }
 
 extern "C" int crr_load_states_verify_host(const crr_state_batch* in, const crr_stored_checksum* stored,
                                            int64_t invalidate_before_ns, crr_verify_row* result, int threads) {
   if (!in || (in->n_wf && !result)) return -1;
-  Ctx c;
+  Owned<Ctx> c;
   const int rc = run_load(in, threads, c);
   if (rc != 0) return rc;
   parallel_for(in->n_wf, threads, [&](uint32_t w, Frame* stk) {
     verify_wf(c, w, kCrcTab.v, stored, invalidate_before_ns, result, stk);
   });
-  free(c.s);
   return 0;
 }

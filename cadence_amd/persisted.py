@@ -434,14 +434,11 @@ class _ImageBuffers:
         self.status = np.zeros(n, np.int32)
         self.flags = np.zeros(n, np.uint32)
         self.c = abi.CLoadImage()
-
-        def ptr(a):
-            return a.ctypes.data if a.size else None
-        self.c.exec = ptr(self.exec)
+        self.c.exec = _ptr(self.exec)
         for t, name in enumerate(abi.LOAD_ROW_TABLES):
-            self.c.rows[t] = ptr(self.rows[name])
+            self.c.rows[t] = _ptr(self.rows[name])
         for f in ("offsets", "tokens", "key_off", "key_len", "key_bytes", "status", "flags"):
-            setattr(self.c, f, ptr(getattr(self, f)))
+            setattr(self.c, f, _ptr(getattr(self, f)))
 
     def image(self, S: abi.CLoadSummary) -> LoadedImage:
         img = LoadedImage(self.exec, self.rows, self.status == 0, None, self.offsets, self.tokens, self.key_off,
@@ -483,19 +480,42 @@ def _host_lib():
     return L
 
 
+def _ptr(a):
+    """The address of an array; None for None or an empty one."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _ref(c):
+    return ctypes.byref(c) if c is not None else None
+
+
+def _host_batch(sbs: StateBlobSet) -> abi.CStateBatch:
+    return _c_batch(sbs, lambda a: a.ctypes.data)
+
+
+def _host_call(name: str, *args) -> None:
+    rc = getattr(_host_lib(), name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: {rc}")
+
+
+def _two_calls(name: str, head, sizing, tail, outputs):
+    """Sizes, allocate, write: ``name(*head, *sizing, *tail)`` fills the sizes struct ``tail`` points to; ``outputs()``
+    then allocates exactly from it and returns (what the caller keeps, the arguments in place of ``sizing``)."""
+    _host_call(name, *head, *sizing, *tail)
+    kept, args = outputs()
+    _host_call(name, *head, *args, *tail)
+    return kept
+
+
 def load_states_host(sbs: StateBlobSet, threads: int = 1) -> LoadedImage:
     """Decode with the host restatement (``crr_load_states_host``); ``interners`` come from the dictionaries."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
-    S = abi.CLoadSummary()
-    rc = L.crr_load_states_host(ctypes.byref(c), None, ctypes.byref(S), threads)   # sizes
-    if rc != 0:
-        raise RuntimeError(f"crr_load_states_host failed: {rc}")
-    buf = _ImageBuffers(S)
-    rc = L.crr_load_states_host(ctypes.byref(c), ctypes.byref(buf.c), ctypes.byref(S), threads)
-    if rc != 0:
-        raise RuntimeError(f"crr_load_states_host failed: {rc}")
-    return buf.image(S)
+    c, S = _host_batch(sbs), abi.CLoadSummary()
+
+    def outputs():
+        buf = _ImageBuffers(S)
+        return buf, (ctypes.byref(buf.c),)
+    return _two_calls("crr_load_states_host", (ctypes.byref(c),), (None,), (ctypes.byref(S), threads), outputs).image(S)
 
 
 def stored_checksums(entries: Sequence) -> np.ndarray:
@@ -524,14 +544,10 @@ def _stored_array(stored, n_wf: int) -> Optional[np.ndarray]:
 def load_states_verify_host(sbs: StateBlobSet, stored=None, invalidate_before_ns: int = 0, threads: int = 1) -> np.ndarray:
     """The check ``mutableStateBuilder.Load`` makes of every state of ``sbs`` (``crr_load_states_verify_host``):
     ``abi.VERIFY_ROW`` per workflow.  ``stored``: ``abi.STORED_CHECKSUM`` rows (``stored_checksums``); None: compute only."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    c = _host_batch(sbs)
     st = _stored_array(stored, sbs.n_wf)
     out = np.zeros(sbs.n_wf, abi.VERIFY_ROW)
-    rc = L.crr_load_states_verify_host(ctypes.byref(c), st.ctypes.data if st is not None and st.size else None,
-                                       int(invalidate_before_ns), out.ctypes.data if out.size else None, threads)
-    if rc != 0:
-        raise RuntimeError(f"crr_load_states_verify_host failed: {rc}")
+    _host_call("crr_load_states_verify_host", ctypes.byref(c), _ptr(st), int(invalidate_before_ns), _ptr(out), threads)
     return out
 
 
@@ -562,23 +578,17 @@ class Branches:
 
 def load_branches_host(sbs: StateBlobSet, threads: int = 1) -> Branches:
     """The branch table by the host restatement (``crr_load_branches_host``)."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
-    P = abi.CLoadNdcSizes()
-    rc = L.crr_load_branches_host(ctypes.byref(c), None, ctypes.byref(P), threads)   # sizes
-    if rc != 0:
-        raise RuntimeError(f"crr_load_branches_host failed: {rc}")
-    out = Branches(np.zeros(int(P.n_branches), abi.NDC_BRANCH), np.zeros(int(P.n_items), abi.VH_ITEM),
-                   np.zeros(int(P.n_branches), abi.BRANCH_TOKEN), np.zeros(int(P.n_wf) + 1, np.int64),
-                   np.zeros(int(P.n_wf), np.int32))
-    d = abi.CLoadBranches()
-    for f in ("branches", "items", "tokens", "branch_begin", "current"):
-        a = getattr(out, f)
-        setattr(d, f, a.ctypes.data if a.size else None)
-    rc = L.crr_load_branches_host(ctypes.byref(c), ctypes.byref(d), ctypes.byref(P), threads)
-    if rc != 0:
-        raise RuntimeError(f"crr_load_branches_host failed: {rc}")
-    return out
+    c, P = _host_batch(sbs), abi.CLoadNdcSizes()
+
+    def outputs():
+        out = Branches(np.zeros(int(P.n_branches), abi.NDC_BRANCH), np.zeros(int(P.n_items), abi.VH_ITEM),
+                       np.zeros(int(P.n_branches), abi.BRANCH_TOKEN), np.zeros(int(P.n_wf) + 1, np.int64),
+                       np.zeros(int(P.n_wf), np.int32))
+        d = abi.CLoadBranches()
+        for f in ("branches", "items", "tokens", "branch_begin", "current"):
+            setattr(d, f, _ptr(getattr(out, f)))
+        return out, (ctypes.byref(d),)
+    return _two_calls("crr_load_branches_host", (ctypes.byref(c),), (None,), (ctypes.byref(P), threads), outputs)
 
 
 # ---- the checksum to store once a routed task is committed (include/cadence_load_store.h) ----------------------
@@ -615,24 +625,26 @@ def _task_arrays(tasks, last_events, results=None, routes=None):
     return out
 
 
+def _store_args(sbs: StateBlobSet, tasks, last_events, results, routes, after):
+    """What the store-family host calls begin with: (the arguments up to the after-image, the number of tasks, what
+    those arguments point into -- to be kept until the last call returns)."""
+    c = _host_batch(sbs)
+    arrays = _task_arrays(tasks, last_events, results, routes)
+    img, keep = _after_image(after, sbs.n_wf)
+    tasks, last, results, routes = (_ptr(a) for a in arrays)
+    n = int(arrays[0].shape[0])
+    return (ctypes.byref(c), tasks, last, n, results, routes, _ref(img)), n, (arrays, keep)
+
+
 def store_checksums_host(sbs: StateBlobSet, tasks, last_events, results, routes, after: Optional[LoadedStates] = None,
                          threads: int = 1) -> np.ndarray:
     """The checksum to store with each task's state once the task is committed, by the host restatement
     (``crr_load_store_checksums_host``): ``abi.STORE_ROW`` per task.  ``results`` / ``routes``: the decisions of
     ``ndc_prepare``; ``last_events``: ``abi.LAST_EVENT`` per task; ``after``: the states the resumed replay left
     (``ReplayResult.to_loaded``), None: no task can be ``APPLIED``."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
-    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
-    img, _keep = _after_image(after, sbs.n_wf)
-    out = np.zeros(tasks.shape[0], abi.STORE_ROW)
-
-    def ptr(a):
-        return a.ctypes.data if a.size else None
-    rc = L.crr_load_store_checksums_host(ctypes.byref(c), ptr(tasks), ptr(last), int(tasks.shape[0]), ptr(results), ptr(routes),
-                                         ctypes.byref(img) if img is not None else None, ptr(out), threads)
-    if rc != 0:
-        raise RuntimeError(f"crr_load_store_checksums_host failed: {rc}")
+    head, n, _keep = _store_args(sbs, tasks, last_events, results, routes, after)
+    out = np.zeros(n, abi.STORE_ROW)
+    _host_call("crr_load_store_checksums_host", *head, _ptr(out), threads)
     return out
 
 
@@ -643,26 +655,14 @@ def store_version_histories_host(sbs: StateBlobSet, tasks, last_events, results,
     122 of the execution blob), by the host restatement (``crr_load_store_vh_host``), arguments as
     ``store_checksums_host``: ``(rows abi.VH_BLOB_ROW[n], blob_off uint64[n + 1], bytes uint8[blob_off[n]])`` -- task
     k's blob is ``bytes[blob_off[k]:blob_off[k + 1]]``, empty unless its outcome is ``APPLIED`` or ``BACKFILLED``."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
-    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
-    img, _keep = _after_image(after, sbs.n_wf)
-    n = int(tasks.shape[0])
+    head, n, _keep = _store_args(sbs, tasks, last_events, results, routes, after)
     P = abi.CVhBlobSizes()
 
-    def ptr(a):
-        return a.ctypes.data if a.size else None
-
-    def call(rows, off, out):
-        rc = L.crr_load_store_vh_host(ctypes.byref(c), ptr(tasks), ptr(last), n, ptr(results), ptr(routes),
-                                      ctypes.byref(img) if img is not None else None, rows, off, out[0], out[1],
-                                      ctypes.byref(P), threads)
-        if rc != 0:
-            raise RuntimeError(f"crr_load_store_vh_host failed: {rc}")
-    call(None, None, (None, 0))   # sizes
-    rows, off = np.zeros(n, abi.VH_BLOB_ROW), np.zeros(n + 1, np.uint64)
-    out = np.zeros((int(P.n_bytes) + 15) // 16 * 16, np.uint8)
-    call(ptr(rows), off.ctypes.data, (ptr(out), out.size))
+    def outputs():
+        rows, off = np.zeros(n, abi.VH_BLOB_ROW), np.zeros(n + 1, np.uint64)
+        out = np.zeros((int(P.n_bytes) + 15) // 16 * 16, np.uint8)
+        return (rows, off, out), (_ptr(rows), off.ctypes.data, _ptr(out), out.size)
+    rows, off, out = _two_calls("crr_load_store_vh_host", head, (None, None, None, 0), (ctypes.byref(P), threads), outputs)
     return rows, off, out[:int(P.n_bytes)].copy()
 
 
@@ -708,10 +708,10 @@ def _mutation_buffers(P: abi.CMutationSizes):
     up = {n: np.zeros(int(P.n_upsert[t]), _ROW_DTYPES[n]) for t, n in enumerate(abi.MUTATION_MAPS)}
     de = {n: np.zeros(int(P.n_delete[t]), np.int64) for t, n in enumerate(abi.MUTATION_MAPS)}
     o = abi.CMutationOut()
-    o.exec, o.exec_capacity = (ex.ctypes.data if ex.size else None), ex.shape[0]
+    o.exec, o.exec_capacity = _ptr(ex), ex.shape[0]
     for t, n in enumerate(abi.MUTATION_MAPS):
-        o.upsert[t], o.upsert_capacity[t] = (up[n].ctypes.data if up[n].size else None), up[n].shape[0]
-        o.deleted[t], o.delete_capacity[t] = (de[n].ctypes.data if de[n].size else None), de[n].shape[0]
+        o.upsert[t], o.upsert_capacity[t] = _ptr(up[n]), up[n].shape[0]
+        o.deleted[t], o.delete_capacity[t] = _ptr(de[n]), de[n].shape[0]
     return ex, up, de, o
 
 
@@ -719,26 +719,14 @@ def mutation_host(sbs: StateBlobSet, tasks, last_events, results, routes, after:
                   threads: int = 1) -> Mutation:
     """The pending-entry mutation to store with each task's state once the task is committed, by the host restatement
     (``crr_load_mutation_host``), arguments as ``store_checksums_host``."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
-    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
-    img, _keep = _after_image(after, sbs.n_wf)
-    n = int(tasks.shape[0])
+    head, n, _keep = _store_args(sbs, tasks, last_events, results, routes, after)
     P = abi.CMutationSizes()
 
-    def ptr(a):
-        return a.ctypes.data if a.size else None
-
-    def call(rows, out):
-        rc = L.crr_load_mutation_host(ctypes.byref(c), ptr(tasks), ptr(last), n, ptr(results), ptr(routes),
-                                      ctypes.byref(img) if img is not None else None, rows, out, ctypes.byref(P), threads)
-        if rc != 0:
-            raise RuntimeError(f"crr_load_mutation_host failed: {rc}")
-    call(None, None)   # sizes
-    rows = np.zeros(n, abi.MUTATION_ROW)
-    ex, up, de, o = _mutation_buffers(P)
-    call(ptr(rows), ctypes.byref(o))
-    return Mutation(rows, ex, up, de)
+    def outputs():
+        rows = np.zeros(n, abi.MUTATION_ROW)
+        ex, up, de, o = _mutation_buffers(P)
+        return Mutation(rows, ex, up, de), (_ptr(rows), ctypes.byref(o))
+    return _two_calls("crr_load_mutation_host", head, (None, None), (ctypes.byref(P), threads), outputs)
 
 
 # ---- the execution blob to store with them (include/cadence_load_store_exec.h) -----------------------------------
@@ -766,34 +754,22 @@ def store_executions_host(sbs: StateBlobSet, tasks, last_events, results, routes
     (None: a request id of the task leaves the blob to the host); ``upserts`` per workflow whether the task's events
     hold an UpsertWorkflowSearchAttributes.  ``(rows abi.EXEC_BLOB_ROW[n], blob_off uint64[n + 1], bytes uint8[])``
     -- task k's blob is ``bytes[blob_off[k]:blob_off[k + 1]]``, empty unless the device encodes it."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
-    tasks, last, results, routes = _task_arrays(tasks, last_events, results, routes)
+    head, n, _keep = _store_args(sbs, tasks, last_events, results, routes, after)
     xt = np.ascontiguousarray(exec_tasks, dtype=abi.EXEC_BLOB_TASK)
-    n = int(tasks.shape[0])
     if xt.shape != (n,):
         raise ValueError(f"{xt.shape} exec_tasks rows for {n} tasks")
-    img, _keep = _after_image(after, sbs.n_wf)
-    tb = _c_task_blobs(task_blobs, lambda a: a.ctypes.data if a.size else None) if task_blobs is not None else None
+    tb = _c_task_blobs(task_blobs, _ptr) if task_blobs is not None else None
     up = None if upserts is None else np.ascontiguousarray(upserts, dtype=np.uint8)
     if up is not None and up.shape != (sbs.n_wf,):
         raise ValueError(f"{up.shape} upsert flags for {sbs.n_wf} workflows")
     P = abi.CExecBlobSizes()
 
-    def ptr(a):
-        return a.ctypes.data if a is not None and a.size else None
-
-    def call(rows, off, out):
-        rc = L.crr_load_store_exec_host(ctypes.byref(c), ptr(tasks), ptr(last), n, ptr(results), ptr(routes),
-                                        ctypes.byref(img) if img is not None else None, ptr(xt),
-                                        ctypes.byref(tb) if tb is not None else None, ptr(up), rows, off, out[0], out[1],
-                                        ctypes.byref(P), threads)
-        if rc != 0:
-            raise RuntimeError(f"crr_load_store_exec_host failed: {rc}")
-    call(None, None, (None, 0))   # sizes
-    rows, off = np.zeros(n, abi.EXEC_BLOB_ROW), np.zeros(n + 1, np.uint64)
-    out = np.zeros(max(int(P.n_bytes), 1), np.uint8)
-    call(ptr(rows), off.ctypes.data, (out.ctypes.data, int(P.n_bytes)))
+    def outputs():
+        rows, off = np.zeros(n, abi.EXEC_BLOB_ROW), np.zeros(n + 1, np.uint64)
+        out = np.zeros(max(int(P.n_bytes), 1), np.uint8)
+        return (rows, off, out), (_ptr(rows), off.ctypes.data, out.ctypes.data, int(P.n_bytes))
+    rows, off, out = _two_calls("crr_load_store_exec_host", (*head, _ptr(xt), _ref(tb), _ptr(up)), (None, None, None, 0),
+                                (ctypes.byref(P), threads), outputs)
     return rows, off, out[:int(P.n_bytes)].copy()
 
 
@@ -859,11 +835,8 @@ class _ResumeBuffers:
         self.key_off, self.key_len = np.zeros(int(P.n_keys), np.uint64), np.zeros(int(P.n_keys), np.uint32)
         self.task_of = np.zeros(n, np.int32)
         self.c = abi.CLoadResumeOut()
-
-        def ptr(a):
-            return a.ctypes.data if a.size else None
         for f in ("bytes", "blob_off", "wf", "key_begin", "key_count", "key_off", "key_len", "task_of"):
-            setattr(self.c, f, ptr(getattr(self, f)))
+            setattr(self.c, f, _ptr(getattr(self, f)))
         self.c.bytes_capacity, self.c.blob_capacity, self.c.key_capacity = int(P.n_bytes), int(P.n_blobs), int(P.n_keys)
 
 
@@ -884,14 +857,13 @@ def load_resume_host(sbs: StateBlobSet, tasks, routes, task_blobs, counts: Optio
     (``crr_load_resume_host``): ``routes`` ``abi.NDC_ROUTE`` per task, ``task_blobs`` a ``blobs.BlobSet`` whose
     workflow k holds task k's event blobs; ``counts`` (``resume_counts_of``) adds the descriptors, the arena and the
     totals."""
-    L = _host_lib()
-    c = _c_batch(sbs, lambda a: a.ctypes.data)
+    c = _host_batch(sbs)
     tasks = np.ascontiguousarray(tasks, dtype=abi.REPL_TASK)
     routes = np.ascontiguousarray(routes, dtype=abi.NDC_ROUTE)
     n = int(tasks.shape[0])
     if routes.shape != (n,):
         raise ValueError(f"{routes.shape} routes for {n} tasks")
-    tb = _c_task_blobs(task_blobs, lambda a: a.ctypes.data if a.size else None)
+    tb = _c_task_blobs(task_blobs, _ptr)
     P, Q = abi.CLoadResumeSizes(), abi.CLoadResumeTotals()
     cnt = None
     if counts is not None:
@@ -899,20 +871,15 @@ def load_resume_host(sbs: StateBlobSet, tasks, routes, task_blobs, counts: Optio
         if cnt.shape != (abi.RESUME_COUNT_ROWS, sbs.n_wf):
             raise ValueError(f"{cnt.shape} counts for {sbs.n_wf} workflows")
 
-    def ptr(a):
-        return a.ctypes.data if a is not None and a.size else None
-
-    def call(rows, out, wf, arena, cap):
-        rc = L.crr_load_resume_host(ctypes.byref(c), ptr(tasks), ptr(routes), n, ctypes.byref(tb), ptr(cnt), rows, out, wf,
-                                    arena, cap, ctypes.byref(P), ctypes.byref(Q), threads)
-        if rc != 0:
-            raise RuntimeError(f"crr_load_resume_host failed: {rc}")
-    call(None, None, None, None, 0)   # sizes
-    rows = np.zeros(n, abi.LOAD_RESUME_ROW)
-    buf = _ResumeBuffers(P)
-    desc = np.zeros(sbs.n_wf, abi.WORKFLOW) if cnt is not None else None
-    arena = np.zeros(int(P.token_bytes), np.uint8) if cnt is not None else None
-    call(ptr(rows), ctypes.byref(buf.c), ptr(desc), ptr(arena), int(P.token_bytes))
+    def outputs():
+        rows = np.zeros(n, abi.LOAD_RESUME_ROW)
+        buf = _ResumeBuffers(P)
+        desc = np.zeros(sbs.n_wf, abi.WORKFLOW) if cnt is not None else None
+        arena = np.zeros(int(P.token_bytes), np.uint8) if cnt is not None else None
+        return (rows, buf, desc, arena), (_ptr(rows), ctypes.byref(buf.c), _ptr(desc), _ptr(arena), int(P.token_bytes))
+    rows, buf, desc, arena = _two_calls("crr_load_resume_host",
+                                        (ctypes.byref(c), _ptr(tasks), _ptr(routes), n, ctypes.byref(tb), _ptr(cnt)),
+                                        (None, None, None, None, 0), (ctypes.byref(P), ctypes.byref(Q), threads), outputs)
     return ResumeImage(P, rows, buf.bytes, buf.blob_off, buf.wf, buf.key_begin, buf.key_count, buf.key_off, buf.key_len,
                        buf.task_of, desc, arena, [int(x) for x in Q.table_rows] if cnt is not None else None)
 

@@ -4,18 +4,14 @@ include/cadence_load_ndc.h), against the values the test wrote: branches, items,
 for the states that do not load.  ``encode_states(branches=...)`` is additive: without it the bytes are as before.
 A stand-alone program runs the same extraction under AddressSanitizer / UndefinedBehaviorSanitizer.
 """
-import os
-import subprocess
-
 import numpy as np
 
 from cadence_amd import abi, persisted
 from cadence_amd.persisted import load_branches_host, load_states_host
 
+import asan_tool
 import load_cases as lc
 import ndc_load_cases as nc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_host_extraction_returns_exactly_what_was_written():
@@ -78,10 +74,4 @@ def test_branches_argument_is_additive():
 
 
 def test_host_extraction_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "load_branches_asan")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_branches_asan.cpp"),
-                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "no sanitizer report" in p.stdout
+    asan_tool.build_and_run(tmp_path, "load_branches_asan")

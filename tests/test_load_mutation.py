@@ -6,7 +6,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 
@@ -14,6 +13,7 @@ from cadence_amd import abi, persisted
 from cadence_amd.persisted import (apply_mutation, load_states_host, load_states_verify_host, mutation_host,
                                    store_checksums_host, store_version_histories_host)
 
+import asan_tool
 import mutation_cases as mc
 import store_cases as sc
 
@@ -347,10 +347,4 @@ def test_failed_replays_and_garbage_counts_stay_within_the_image():
 
 
 def test_host_restatement_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "load_mutation_asan")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_mutation_asan.cpp"),
-                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "no sanitizer report" in p.stdout
+    asan_tool.build_and_run(tmp_path, "load_mutation_asan")

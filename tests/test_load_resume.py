@@ -5,12 +5,12 @@ outcome, and the stand-alone sanitizer program.
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
 from cadence_amd import abi, blobs, persisted
 
+import asan_tool
 import load_resume_cases as rc_
 import store_cases as sc
 
@@ -132,9 +132,4 @@ def test_blob_ranges_outside_the_task_batch_read_as_no_blobs():
 
 
 def test_host_restatement_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "load_resume_asan")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_resume_asan.cpp"),
-                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    assert "no sanitizer report" in out and "24 batches" in out
+    assert "24 batches" in asan_tool.build_and_run(tmp_path, "load_resume_asan")

@@ -12,6 +12,7 @@ import pytest
 from cadence_amd import abi, persisted
 from cadence_amd.persisted import build_blob_set, encode_states, load_states_host
 
+import asan_tool
 import load_cases as lc
 
 
@@ -231,3 +232,7 @@ def test_libraries_export_the_loader_and_reject_bad_arguments():
     sbs.wf["blob_begin"][1] += 1            # ranges that are not consecutive
     c = persisted._c_batch(sbs, lambda a: a.ctypes.data)
     assert host.crr_load_states_host(ctypes.byref(c), None, ctypes.byref(S), 1) == -1
+
+
+def test_host_restatement_under_asan_and_ubsan(tmp_path):
+    assert "6 full blobs OK, 1033 truncations malformed" in asan_tool.build_and_run(tmp_path, "load_states_asan")

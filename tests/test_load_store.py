@@ -10,13 +10,13 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 
 from cadence_amd import abi, persisted
 from cadence_amd.persisted import load_states_verify_host, store_checksums_host
 
+import asan_tool
 import store_cases as sc
 import verify_cases as vc
 
@@ -176,10 +176,4 @@ def test_empty_batch_and_no_tasks():
 
 
 def test_host_restatement_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "load_store_asan")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_store_asan.cpp"),
-                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "no sanitizer report" in p.stdout
+    asan_tool.build_and_run(tmp_path, "load_store_asan")

@@ -6,7 +6,6 @@ again."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 
@@ -14,6 +13,7 @@ from cadence_amd import abi, persisted
 from cadence_amd.persisted import (apply_mutation, load_states_host, load_states_verify_host, mutation_host,
                                    store_checksums_host, store_executions_host, store_version_histories_host)
 
+import asan_tool
 import exec_blob_cases as xc
 import mutation_cases as mc
 import store_cases as sc
@@ -265,10 +265,4 @@ def test_round_trip_device_blobs_load_as_the_snapshot():
 
 
 def test_host_restatement_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "load_store_exec_asan")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_store_exec_asan.cpp"),
-                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "no sanitizer report" in p.stdout
+    asan_tool.build_and_run(tmp_path, "load_store_exec_asan")

@@ -12,7 +12,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ from cadence_amd import abi, persisted
 from cadence_amd.persisted import (load_branches_host, load_states_host, load_states_verify_host, store_checksums_host,
                                    store_version_histories_host)
 
+import asan_tool
 import ndc_load_cases as nc
 import store_cases as sc
 import verify_cases as vc
@@ -329,10 +329,4 @@ def test_header_pins_and_bad_arguments():
 
 
 def test_host_restatement_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "load_store_vh_asan")
-    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "load_store_vh_asan.cpp"),
-                    os.path.join(ROOT, "cadence_amd", "csrc", "load_states.cpp"), "-o", exe, "-lpthread"], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stdout + p.stderr
-    assert "no sanitizer report" in p.stdout
+    asan_tool.build_and_run(tmp_path, "load_store_vh_asan")

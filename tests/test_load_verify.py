@@ -10,6 +10,7 @@ import pytest
 from cadence_amd import abi, persisted
 from cadence_amd.persisted import load_states_verify_host, stored_checksums
 
+import asan_tool
 import load_cases as lc
 import verify_cases as vc
 
@@ -123,3 +124,7 @@ def test_libraries_export_the_verify_entry_points_and_reject_bad_arguments():
     sbs.wf["blob_begin"][1] += 1            # ranges that are not consecutive
     c = persisted._c_batch(sbs, lambda a: a.ctypes.data)
     assert host.crr_load_states_verify_host(ctypes.byref(c), None, 0, out.ctypes.data, 1) == -1
+
+
+def test_host_restatement_under_asan_and_ubsan(tmp_path):
+    assert "128 full states match, 306 truncations not loaded" in asan_tool.build_and_run(tmp_path, "load_verify_asan")

@@ -21,36 +21,15 @@
 
 #include "cadence_load_ndc.h"
 
-namespace {
+#include "load_asan_common.h"
 
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list(int16_t id, uint8_t elem, size_t n) { field(15, id), u8(elem), be(n, 4); }
-  void stop() { u8(0); }
-};
+namespace {
 
 struct Branch {
   bool has_token, has_items;
   std::string token;
   std::vector<std::pair<int64_t, int64_t>> items;
 };
-
-std::string bytes_of(size_t n, int seed) {
-  std::string s;
-  for (size_t i = 0; i < n; ++i) s.push_back((char)(uint8_t)(seed + 7 * i));
-  return s;
-}
 
 std::string version_histories(int32_t current, const std::vector<Branch>& hs) {
   Wr w;
@@ -89,17 +68,11 @@ struct Table {
 Table extract(const std::string& exec) {
   Wr timer;
   timer.i64(10, 3), timer.i64(12, 7), timer.stop();
-  const std::vector<std::string> blobs = {timer.b, exec};
-  const crr_state_blob meta[2] = {{CRR_STATE_TIMER, 5, 0, 0, 0}, {CRR_STATE_EXECUTION, 0, 0, 0, 0}};
-  size_t total = 0;
-  std::vector<uint64_t> off{0};
-  for (auto& b : blobs) off.push_back(total += b.size());
-  uint8_t* bytes = static_cast<uint8_t*>(malloc(total));   // exactly the blobs: no pad to hide an over-read
-  size_t o = 0;
-  for (auto& b : blobs) memcpy(bytes + o, b.data(), b.size()), o += b.size();
-  const crr_state_wf wf = {0, 2, 20};
-  const uint8_t strings[5] = {'t', 'i', 'm', 'e', 'r'};
-  const crr_state_batch in = {bytes, off.data(), meta, &wf, strings, 2, 1};
+  Packed blobs;   // exactly the blobs: no pad to hide an over-read
+  blobs.add(timer.b), blobs.add(exec);
+  const StateBatch batch(blobs.bytes, blobs.off, {{CRR_STATE_TIMER, 5, 0, 0, 0}, {CRR_STATE_EXECUTION, 0, 0, 0, 0}}, {{0, 2, 20}},
+                         {'t', 'i', 'm', 'e', 'r'});
+  const crr_state_batch& in = batch.in;
   Table T;
   T.current = -7;
   T.rc = crr_load_branches_host(&in, nullptr, &T.sizes, 1);
@@ -121,8 +94,7 @@ Table extract(const std::string& exec) {
     T.current = *d.current;
     free(d.branches), free(d.items), free(d.tokens), free(d.branch_begin), free(d.current);
   }
-  T.bytes.assign(reinterpret_cast<const char*>(bytes), total);
-  free(bytes);
+  T.bytes.assign(blobs.bytes.begin(), blobs.bytes.end());
   return T;
 }
 

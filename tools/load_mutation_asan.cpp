@@ -24,24 +24,9 @@
 
 #include "cadence_load_mutation.h"
 
-namespace {
+#include "load_asan_common.h"
 
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list(int16_t id, uint8_t elem, size_t n) { field(15, id), u8(elem), be(n, 4); }
-  void stop() { u8(0); }
-};
+namespace {
 
 std::string execution_blob(int n_points) {
   Wr vh;
@@ -56,13 +41,6 @@ std::string execution_blob(int n_points) {
   w.str(115, rp.b), w.str(116, "thriftrw"), w.str(122, vh.b), w.str(124, "thriftrw");
   w.stop();
   return w.b;
-}
-
-template <class T>
-T* exact(const std::vector<T>& v) {   // a heap block of exactly the vector's bytes (malloc(0): no byte may be touched)
-  T* p = static_cast<T*>(malloc(v.size() * sizeof(T)));
-  if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-  return p;
 }
 
 // ---- this file's own comparison of the persisted fields, by name ------------------------------------------------
@@ -233,18 +211,13 @@ int check(uint32_t n_wf, int shape, int* n_rows) {
     wf.push_back({first, (uint32_t)meta.size() - first, 60});
   }
   bytes.resize(bytes.size() + 32, 0);   // readable CRR_INGEST_PAD bytes past the last blob, as the interface asks
-  uint8_t* d_bytes = exact(bytes);
-  uint64_t* d_off = exact(off);
-  crr_state_blob* d_meta = exact(meta);
-  crr_state_wf* d_wf = exact(wf);
-  uint8_t* d_strings = exact(strings);
-  const crr_state_batch in = {d_bytes, d_off, d_meta, d_wf, d_strings, (uint32_t)meta.size(), n_wf};
+  const StateBatch batch(bytes, off, meta, wf, strings);
+  const crr_state_batch& in = batch.in;
 
   // the image before, by the loader
   crr_load_summary S;
   if (crr_load_states_host(&in, nullptr, &S, 1) != 0) return fail("sizing the load");
-  crr_load_image B;
-  memset(&B, 0, sizeof B);
+  Image B;
   const size_t row_bytes[7] = {sizeof(crr_activity_row), sizeof(crr_timer_row), sizeof(crr_child_row), sizeof(crr_initiated_row),
                                sizeof(crr_initiated_row), sizeof(crr_vh_item), sizeof(crr_reset_point_row)};
   B.exec = static_cast<crr_exec_row*>(malloc(n_wf * sizeof(crr_exec_row)));
@@ -317,8 +290,7 @@ int check(uint32_t n_wf, int shape, int* n_rows) {
   const int64_t totals[7] = {(int64_t)act.size(), (int64_t)timer.size(), (int64_t)child.size(), (int64_t)rc.size(),
                              (int64_t)sig.size(), (int64_t)vh.size(), (int64_t)rp.size()};
   for (int k = 0; k < 7; ++k) o2[(size_t)k * (n_wf + 1) + n_wf] = totals[k];
-  crr_load_image A;
-  memset(&A, 0, sizeof A);
+  Image A;
   A.exec = exact(ex), A.offsets = exact(o2);
   A.rows[0] = exact(act), A.rows[1] = exact(timer), A.rows[2] = exact(child), A.rows[3] = exact(rc), A.rows[4] = exact(sig);
   A.rows[5] = exact(vh), A.rows[6] = exact(rp);
@@ -416,9 +388,6 @@ int check(uint32_t n_wf, int shape, int* n_rows) {
     for (int t = 0; t < 5; ++t) free(o.upsert[t]), free(o.deleted[t]);
   }
   free(d_rt), free(d_le), free(d_res), free(d_routes);
-  free(A.exec), free(A.offsets), free(B.exec), free(B.offsets), free(B.status);
-  for (int t = 0; t < 7; ++t) free(A.rows[t]), free(B.rows[t]);
-  free(d_bytes), free(d_off), free(d_meta), free(d_wf), free(d_strings);
   return bad;
 }
 

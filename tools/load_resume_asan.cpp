@@ -23,24 +23,9 @@
 
 #include "cadence_load_resume.h"
 
-namespace {
+#include "load_asan_common.h"
 
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list(int16_t id, uint8_t elem, size_t n) { field(15, id), u8(elem), be(n, 4); }
-  void stop() { u8(0); }
-};
+namespace {
 
 std::string execution_blob(int n_points, const std::string& token) {
   Wr vh;
@@ -56,13 +41,6 @@ std::string execution_blob(int n_points, const std::string& token) {
   w.str(115, rp.b), w.str(116, "thriftrw"), w.str(122, vh.b), w.str(124, "thriftrw");
   w.stop();
   return w.b;
-}
-
-template <class T>
-T* exact(const std::vector<T>& v) {   // a heap block of exactly the vector's bytes (malloc(0): no byte may be touched)
-  T* p = static_cast<T*>(malloc(v.size() * sizeof(T)));
-  if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-  return p;
 }
 
 int fail(const char* what, long a = 0, long b = 0) {
@@ -103,18 +81,13 @@ int check(uint32_t n_wf, int shape, Tally& tally) {
     wf.push_back({first, (uint32_t)meta.size() - first, 60});
   }
   bytes.resize(bytes.size() + 32, 0);   // readable CRR_INGEST_PAD bytes past the last blob, as the loader's interface asks
-  uint8_t* d_bytes = exact(bytes);
-  uint64_t* d_off = exact(off);
-  crr_state_blob* d_meta = exact(meta);
-  crr_state_wf* d_wf = exact(wf);
-  uint8_t* d_strings = exact(strings);
-  const crr_state_batch in = {d_bytes, d_off, d_meta, d_wf, d_strings, (uint32_t)meta.size(), n_wf};
+  const StateBatch batch(bytes, off, meta, wf, strings);
+  const crr_state_batch& in = batch.in;
 
   // the loaded image, by the loader
   crr_load_summary S;
   if (crr_load_states_host(&in, nullptr, &S, 1) != 0) return fail("sizing the load");
-  crr_load_image B;
-  memset(&B, 0, sizeof B);
+  Image B;
   B.offsets = static_cast<int64_t*>(malloc((size_t)CRR_LOAD_TABLES * (n_wf + 1) * sizeof(int64_t)));
   B.status = static_cast<int32_t*>(malloc(n_wf * sizeof(int32_t)));
   B.tokens = static_cast<uint8_t*>(malloc((size_t)S.totals[CRR_LOAD_T_TOKEN]));
@@ -306,8 +279,6 @@ int check(uint32_t n_wf, int shape, Tally& tally) {
     free(rows), free(desc), free(arena);
   }
   free(d_tbytes), free(d_toff), free(d_tw), free(d_rt), free(d_routes), free(d_counts);
-  free(B.offsets), free(B.status), free(B.tokens), free(B.key_off), free(B.key_len), free(B.key_bytes);
-  free(d_bytes), free(d_off), free(d_meta), free(d_wf), free(d_strings);
   return bad;
 }
 

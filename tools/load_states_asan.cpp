@@ -17,33 +17,18 @@
 
 #include "cadence_load.h"
 
+#include "load_asan_common.h"
+
 namespace {
 
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void boolean(int16_t id, bool v) { field(2, id), u8(v); }
-  void dbl(int16_t id) { field(4, id), be(0x4000000000000000ull, 8); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list_str(int16_t id, const std::vector<std::string>& v) {
-    field(15, id), u8(11), be(v.size(), 4);
-    for (auto& s : v) be(s.size(), 4), b += s;
-  }
-  void map_str(int16_t id, const std::vector<std::string>& kv) {
-    field(13, id), u8(11), u8(11), be(kv.size() / 2, 4);
-    for (auto& s : kv) be(s.size(), 4), b += s;
-  }
-  void stop() { u8(0); }
-};
+void list_str(Wr& w, int16_t id, const std::vector<std::string>& v) {
+  w.list(id, 11, v.size());
+  for (auto& s : v) w.be(s.size(), 4), w.b += s;
+}
+void map_str(Wr& w, int16_t id, const std::vector<std::string>& kv) {
+  w.field(13, id), w.u8(11), w.u8(11), w.be(kv.size() / 2, 4);
+  for (auto& s : kv) w.be(s.size(), 4), w.b += s;
+}
 
 std::string version_histories() {
   Wr w;
@@ -71,8 +56,8 @@ std::string execution_blob() {
   w.str(12, "parent"), w.i64(16, -23), w.str(24, "task-list"), w.i32(30, 10), w.i32(34, 1), w.i32(36, 0);
   w.i64(48, 777), w.i64(50, 18), w.i64(52, 15), w.i64(58, 3), w.i64(60, 18), w.i64(62, -23), w.i32(64, 10), w.i64(66, 0);
   w.i64(68, -6795364578871345152LL), w.i64(69, 1600000000000000000LL), w.boolean(70, true), w.i64(71, 1600000000000000000LL);
-  w.str(74, "emptyUuid"), w.str(78, "sticky"), w.dbl(92), w.i64(94, 0), w.list_str(96, {"a", "bb"}), w.boolean(98, false);
-  w.i64(106, 2), w.str(115, reset_points()), w.str(116, "thriftrw"), w.map_str(118, {"k", "v", "k2", ""});
+  w.str(74, "emptyUuid"), w.str(78, "sticky"), w.dbl(92), w.i64(94, 0), list_str(w, 96, {"a", "bb"}), w.boolean(98, false);
+  w.i64(106, 2), w.str(115, reset_points()), w.str(116, "thriftrw"), map_str(w, 118, {"k", "v", "k2", ""});
   w.str(122, version_histories()), w.str(124, "thriftrw"), w.stop();
   return w.b;
 }
@@ -83,7 +68,7 @@ std::string pending_blob(uint32_t kind) {
   if (kind == CRR_STATE_ACTIVITY) {
     w.i64(12, 4), w.str(14, "event"), w.i64(18, 1600000000000000005LL), w.i64(20, 6), w.i64(26, 1600000001000000000LL);
     w.str(28, "activity-five"), w.str(30, "request"), w.i32(32, 5), w.i32(34, 30), w.i32(36, 20), w.i32(38, 3), w.boolean(40, true);
-    w.i64(42, 9), w.i32(44, 1), w.i32(46, 2), w.str(48, "tl"), w.boolean(52, true), w.dbl(62), w.list_str(64, {"x"});
+    w.i64(42, 9), w.i32(44, 1), w.i32(46, 2), w.str(48, "tl"), w.boolean(52, true), w.dbl(62), list_str(w, 64, {"x"});
   } else if (kind == CRR_STATE_TIMER) {
     w.i64(12, 7), w.i64(14, 1600000100000000000LL), w.i64(16, 1);
   } else if (kind == CRR_STATE_CHILD) {
@@ -98,23 +83,16 @@ std::string pending_blob(uint32_t kind) {
 
 // one workflow: [a full execution blob unless the cut one is the execution blob,] the cut blob last
 int load_one(uint32_t kind, const std::string& full_exec, const std::string& cut, int32_t* status) {
-  std::vector<std::string> blobs;
+  Packed blobs;   // exactly the blobs: no pad to hide an over-read
   std::vector<crr_state_blob> meta;
   if (kind != CRR_STATE_EXECUTION) {
-    blobs.push_back(full_exec);
+    blobs.add(full_exec);
     meta.push_back({CRR_STATE_EXECUTION, 0, 0, 0, 0});
   }
-  blobs.push_back(cut);
+  blobs.add(cut);
   meta.push_back({kind, kind == CRR_STATE_TIMER ? 5u : 0u, 5, 0, 0});
-  size_t total = 0;
-  std::vector<uint64_t> off{0};
-  for (auto& b : blobs) off.push_back(total += b.size());
-  uint8_t* bytes = static_cast<uint8_t*>(malloc(total ? total : 1));   // exactly the blobs: no pad to hide an over-read
-  size_t o = 0;
-  for (auto& b : blobs) memcpy(bytes + o, b.data(), b.size()), o += b.size();
-  const crr_state_wf wf = {0, (uint32_t)blobs.size(), 20};
-  const uint8_t strings[5] = {'t', 'i', 'm', 'e', 'r'};
-  crr_state_batch in = {bytes, off.data(), meta.data(), &wf, strings, (uint32_t)blobs.size(), 1};
+  const StateBatch batch(blobs.bytes, blobs.off, meta, {{0, (uint32_t)meta.size(), 20}}, {'t', 'i', 'm', 'e', 'r'});
+  const crr_state_batch& in = batch.in;
   crr_load_summary S;
   int rc = crr_load_states_host(&in, nullptr, &S, 1);   // sizes
   if (rc == 0) {
@@ -137,7 +115,6 @@ int load_one(uint32_t kind, const std::string& full_exec, const std::string& cut
     img.key_bytes = kb.data(), img.status = status, img.flags = &flags;
     rc = crr_load_states_host(&in, &img, &S, 1);
   }
-  free(bytes);
   return rc;
 }
 

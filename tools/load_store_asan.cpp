@@ -23,32 +23,11 @@
 
 #include "cadence_load_store.h"
 
+#include "load_asan_common.h"
+
 namespace {
 
 typedef std::vector<std::pair<int64_t, int64_t>> Items;
-
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void boolean(int16_t id, bool v) { field(2, id), u8(v ? 1 : 0); }
-  void i16(int16_t id, int16_t v) { field(6, id), be((uint16_t)v, 2); }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list(int16_t id, uint8_t elem, size_t n) { field(15, id), u8(elem), be(n, 4); }
-  void ids(int16_t id, const std::vector<int64_t>& v) {
-    list(id, 10, v.size());
-    for (int64_t x : v) be((uint64_t)x, 8);
-  }
-  void stop() { u8(0); }
-};
 
 struct Branch {
   bool has_token, has_items;
@@ -64,12 +43,6 @@ struct State {
   std::vector<Branch> hs;
   bool sticky_last;   // the sticky name is the execution blob's last field (else the version histories are)
 };
-
-std::string bytes_of(size_t n, int seed) {
-  std::string s;
-  for (size_t i = 0; i < n; ++i) s.push_back((char)(uint8_t)(seed + 7 * i));
-  return s;
-}
 
 std::string version_histories(int32_t current, const std::vector<Branch>& hs) {
   Wr w;
@@ -115,7 +88,11 @@ std::string payload(const Scalars& x, const std::string& sticky, int32_t current
   w.u8(0x59);
   w.boolean(10, x.cancel), w.i16(15, x.state), w.i64(23, x.last_first), w.i64(24, x.next_event), w.i64(25, x.last_processed);
   w.i64(26, x.signal_count), w.i32(35, x.attempt), w.i64(36, x.decision_version), w.i64(37, x.schedule_id), w.i64(38, x.started_id);
-  w.ids(45, x.timers), w.ids(46, x.acts), w.ids(47, x.sigs), w.ids(48, x.rcs), w.ids(49, x.children);
+  auto ids = [&](int16_t id, const std::vector<int64_t>& v) {
+    w.list(id, 10, v.size());
+    for (int64_t x : v) w.be((uint64_t)x, 8);
+  };
+  ids(45, x.timers), ids(46, x.acts), ids(47, x.sigs), ids(48, x.rcs), ids(49, x.children);
   w.str(55, sticky);
   w.field(12, 56);
   w.i32(10, current), w.list(20, 12, hs.size());
@@ -159,13 +136,6 @@ int add_or_update(Branch& b, int64_t id, int64_t version) {
   return 0;
 }
 
-template <class T>
-T* exact(const std::vector<T>& v) {   // a heap block of exactly the vector's bytes (malloc(0): no byte may be touched)
-  T* p = static_cast<T*>(malloc(v.size() * sizeof(T)));
-  if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-  return p;
-}
-
 struct Task {
   uint32_t wf;
   int32_t route, action, branch;
@@ -202,12 +172,8 @@ int check(const std::vector<State>& states, const std::vector<After>& after, std
   }
   const uint32_t n_wf = (uint32_t)states.size(), n = (uint32_t)tasks.size();
   std::vector<uint8_t> strings = {'t', 'i', 'm', 'e', 'r'};
-  uint8_t* d_bytes = exact(bytes);
-  uint64_t* d_off = exact(off);
-  crr_state_blob* d_meta = exact(meta);
-  crr_state_wf* d_wf = exact(wf);
-  uint8_t* d_strings = exact(strings);
-  const crr_state_batch in = {d_bytes, d_off, d_meta, d_wf, d_strings, (uint32_t)meta.size(), n_wf};
+  const StateBatch batch(bytes, off, meta, wf, strings);
+  const crr_state_batch& in = batch.in;
 
   // the after-image: dense rows in workflow order, exact blocks
   std::vector<crr_exec_row> ex(n_wf);
@@ -244,8 +210,7 @@ int check(const std::vector<State>& states, const std::vector<After>& after, std
     const int64_t total = t == 0 ? (int64_t)act.size() : t == 2 ? (int64_t)child.size() : t == 5 ? (int64_t)vh.size() : 0;
     offsets[(size_t)t * (n_wf + 1) + n_wf] = total;
   }
-  crr_load_image img;
-  memset(&img, 0, sizeof img);
+  Image img;
   img.exec = exact(ex), img.offsets = exact(offsets), img.status = exact(status);
   img.rows[0] = exact(act), img.rows[2] = exact(child), img.rows[5] = exact(vh);
   // the tables without rows: exact blocks of no bytes
@@ -309,9 +274,6 @@ int check(const std::vector<State>& states, const std::vector<After>& after, std
   }
   if (rc != 0) fprintf(stderr, "crr_load_store_checksums_host: %d\n", rc);
   free(out), free(d_rt), free(d_le), free(d_res), free(d_routes);
-  free(img.exec), free(img.offsets), free(img.status);
-  for (int t = 0; t < 6; ++t) free(img.rows[t]);
-  free(d_bytes), free(d_off), free(d_meta), free(d_wf), free(d_strings);
   return bad;
 }
 

@@ -25,24 +25,11 @@
 
 #include "cadence_load_store_exec.h"
 
+#include "load_asan_common.h"
+
 namespace {
 
 const int64_t kGoZero = -6795364578871345152LL;
-
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-};
 
 // one top-level field: its thrift type and its value's bytes as they lie in the blob
 struct Field {
@@ -133,13 +120,6 @@ std::vector<Field> go_shaped(bool with18, const std::string& request) {
   return f;
 }
 
-template <class T>
-T* exact(const std::vector<T>& v) {   // a heap block of exactly the vector's bytes (malloc(0): no byte may be touched)
-  T* p = static_cast<T*>(malloc(v.size() * sizeof(T)));
-  if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-  return p;
-}
-
 struct Task {
   uint32_t wf;
   int32_t route, action;
@@ -205,12 +185,8 @@ int run(int threads, int* blobs_checked, uint64_t* bytes_checked, unsigned* flag
     meta.push_back({CRR_STATE_EXECUTION, 0, 0, 0, 0});
   }
   std::vector<uint8_t> strings = {'s'};
-  uint8_t* d_bytes = exact(bytes);
-  uint64_t* d_off = exact(off);
-  crr_state_blob* d_meta = exact(meta);
-  crr_state_wf* d_wf = exact(wf);
-  uint8_t* d_strings = exact(strings);
-  const crr_state_batch in = {d_bytes, d_off, d_meta, d_wf, d_strings, (uint32_t)meta.size(), n_wf};
+  const StateBatch batch(bytes, off, meta, wf, strings);
+  const crr_state_batch& in = batch.in;
 
   // the after-image: exec rows by hand; the current branch's items per workflow; no pending rows at all, although
   // workflow 0's counts claim INT_MAX of everything (clamped to the tables' zero rows)
@@ -236,8 +212,7 @@ int run(int threads, int* blobs_checked, uint64_t* bytes_checked, unsigned* flag
     for (auto& it : after_items) vh.push_back({it.first, it.second});
   }
   offsets[5 * (n_wf + 1) + n_wf] = (int64_t)vh.size();
-  crr_load_image img;
-  memset(&img, 0, sizeof img);
+  Image img;
   img.exec = exact(ex), img.offsets = exact(offsets), img.status = exact(status);
   img.rows[5] = exact(vh);
   for (int t = 0; t < 7; ++t)
@@ -388,9 +363,6 @@ int run(int threads, int* blobs_checked, uint64_t* bytes_checked, unsigned* flag
           P.n_bytes != 0 || one_off != 0;
   }
   free(d_tbytes), free(d_toff), free(d_twf), free(d_upserts);
-  free(img.exec), free(img.offsets), free(img.status);
-  for (int t = 0; t < 7; ++t) free(img.rows[t]);
-  free(d_bytes), free(d_off), free(d_meta), free(d_wf), free(d_strings);
   return bad;
 }
 

@@ -23,27 +23,11 @@
 
 #include "cadence_load_store_vh.h"
 
+#include "load_asan_common.h"
+
 namespace {
 
 typedef std::vector<std::pair<int64_t, int64_t>> Items;
-
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void boolean(int16_t id, bool v) { field(2, id), u8(v ? 1 : 0); }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list(int16_t id, uint8_t elem, size_t n) { field(15, id), u8(elem), be(n, 4); }
-  void stop() { u8(0); }
-};
 
 struct Branch {
   bool has_token, has_items;
@@ -59,12 +43,6 @@ struct State {
   std::vector<Branch> hs;
   bool sticky_last;   // the sticky name is the execution blob's last field (else the version histories are)
 };
-
-std::string bytes_of(size_t n, int seed) {
-  std::string s;
-  for (size_t i = 0; i < n; ++i) s.push_back((char)(uint8_t)(seed + 7 * i));
-  return s;
-}
 
 // the stored form: a history's absent field is left out; the items first, so that a token can end its struct
 std::string stored_histories(int32_t current, const std::vector<Branch>& hs) {
@@ -122,13 +100,6 @@ int add_or_update(Branch& b, int64_t id, int64_t version) {
   return 0;
 }
 
-template <class T>
-T* exact(const std::vector<T>& v) {   // a heap block of exactly the vector's bytes (malloc(0): no byte may be touched)
-  T* p = static_cast<T*>(malloc(v.size() * sizeof(T)));
-  if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
-  return p;
-}
-
 struct Task {
   uint32_t wf;
   int32_t route, action, branch;
@@ -164,12 +135,8 @@ int check(const std::vector<State>& states, const std::vector<After>& after, std
   }
   const uint32_t n_wf = (uint32_t)states.size(), n = (uint32_t)tasks.size();
   std::vector<uint8_t> strings = {'t', 'i', 'm', 'e', 'r'};
-  uint8_t* d_bytes = exact(bytes);
-  uint64_t* d_off = exact(off);
-  crr_state_blob* d_meta = exact(meta);
-  crr_state_wf* d_wf = exact(wf);
-  uint8_t* d_strings = exact(strings);
-  const crr_state_batch in = {d_bytes, d_off, d_meta, d_wf, d_strings, (uint32_t)meta.size(), n_wf};
+  const StateBatch batch(bytes, off, meta, wf, strings);
+  const crr_state_batch& in = batch.in;
 
   // the after-image: exec rows and vh rows in workflow order, exact blocks; the other tables hold no rows
   std::vector<crr_exec_row> ex(n_wf);
@@ -187,8 +154,7 @@ int check(const std::vector<State>& states, const std::vector<After>& after, std
     for (auto& it : A.vh) vh.push_back({it.first, it.second});
   }
   offsets[5 * (n_wf + 1) + n_wf] = (int64_t)vh.size();
-  crr_load_image img;
-  memset(&img, 0, sizeof img);
+  Image img;
   img.exec = exact(ex), img.offsets = exact(offsets), img.status = exact(status);
   img.rows[5] = exact(vh);
   for (int t = 0; t < 5; ++t) img.rows[t] = malloc(0);
@@ -274,9 +240,6 @@ int check(const std::vector<State>& states, const std::vector<After>& after, std
   *bytes_checked += total;
   free(rows), free(blob_off), free(out);
   free(d_rt), free(d_le), free(d_res), free(d_routes);
-  free(img.exec), free(img.offsets), free(img.status);
-  for (int t = 0; t < 6; ++t) free(img.rows[t]);
-  free(d_bytes), free(d_off), free(d_meta), free(d_wf), free(d_strings);
   return bad;
 }
 

@@ -20,38 +20,15 @@
 
 #include "cadence_load_verify.h"
 
-namespace {
+#include "load_asan_common.h"
 
-struct Wr {
-  std::string b;
-  void u8(uint8_t v) { b.push_back((char)v); }
-  void be(uint64_t v, int n) {
-    for (int i = n - 1; i >= 0; --i) u8((uint8_t)(v >> (8 * i)));
-  }
-  void field(uint8_t t, int16_t id) {
-    u8(t);
-    be((uint16_t)id, 2);
-  }
-  void i16(int16_t id, int16_t v) { field(6, id), be((uint16_t)v, 2); }
-  void i32(int16_t id, int32_t v) { field(8, id), be((uint32_t)v, 4); }
-  void i64(int16_t id, int64_t v) { field(10, id), be((uint64_t)v, 8); }
-  void boolean(int16_t id, bool v) { field(2, id), u8(v); }
-  void str(int16_t id, const std::string& s) { field(11, id), be(s.size(), 4), b += s; }
-  void list(int16_t id, uint8_t elem, size_t n) { field(15, id), u8(elem), be(n, 4); }
-  void stop() { u8(0); }
-};
+namespace {
 
 struct Branch {
   bool has_token;
   std::string token;
   std::vector<std::pair<int64_t, int64_t>> items;
 };
-
-std::string bytes_of(size_t n, int seed) {
-  std::string s;
-  for (size_t i = 0; i < n; ++i) s.push_back((char)(uint8_t)(seed + 7 * i));
-  return s;
-}
 
 std::string version_histories(int32_t current, const std::vector<Branch>& hs) {
   Wr w;
@@ -110,24 +87,17 @@ std::string small_blob(int64_t version, int64_t started_id) {
 
 // one workflow: a timer and two signals, then the execution blob last (its end is the block's end)
 crr_verify_row verify_one(const std::string& exec, const crr_stored_checksum* stored, int64_t cut_off, int* rc) {
-  const std::vector<std::string> blobs = {small_blob(3, 7), small_blob(3, 0), small_blob(3, 0), exec};
-  const crr_state_blob meta[4] = {{CRR_STATE_TIMER, 5, 0, 0, 0}, {CRR_STATE_SIGNAL, 0, 12, 0, 0}, {CRR_STATE_SIGNAL, 0, 9, 0, 0},
-                                  {CRR_STATE_EXECUTION, 0, 0, 0, 0}};
-  size_t total = 0;
-  std::vector<uint64_t> off{0};
-  for (auto& b : blobs) off.push_back(total += b.size());
-  uint8_t* bytes = static_cast<uint8_t*>(malloc(total));   // exactly the blobs: no pad to hide an over-read
-  size_t o = 0;
-  for (auto& b : blobs) memcpy(bytes + o, b.data(), b.size()), o += b.size();
-  const crr_state_wf wf = {0, 4, 20};
-  const uint8_t strings[5] = {'t', 'i', 'm', 'e', 'r'};
-  const crr_state_batch in = {bytes, off.data(), meta, &wf, strings, 4, 1};
+  Packed blobs;   // exactly the blobs: no pad to hide an over-read
+  for (auto& b : {small_blob(3, 7), small_blob(3, 0), small_blob(3, 0), exec}) blobs.add(b);
+  const StateBatch batch(blobs.bytes, blobs.off,
+                         {{CRR_STATE_TIMER, 5, 0, 0, 0}, {CRR_STATE_SIGNAL, 0, 12, 0, 0}, {CRR_STATE_SIGNAL, 0, 9, 0, 0},
+                          {CRR_STATE_EXECUTION, 0, 0, 0, 0}},
+                         {{0, 4, 20}}, {'t', 'i', 'm', 'e', 'r'});
   crr_verify_row* out = static_cast<crr_verify_row*>(malloc(sizeof(crr_verify_row)));   // exactly one row
   memset(out, 0xEE, sizeof *out);
-  *rc = crr_load_states_verify_host(&in, stored, cut_off, out, 1);
+  *rc = crr_load_states_verify_host(&batch.in, stored, cut_off, out, 1);
   const crr_verify_row r = *out;
   free(out);
-  free(bytes);
   return r;
 }
 
