@@ -16,13 +16,13 @@ import pytest
 from cadence_amd import abi
 from cadence_amd.abi import EventType as ET
 from cadence_amd.flatten import flatten, interleave
-from cadence_amd.history import WorkflowHistory, det_uuid
+from cadence_amd.history import det_uuid
 from cadence_amd.result import diff_results, to_canonical_order
-from cadence_amd.synth_mixed import BASE_TS, _Walk
+from cadence_amd.synth_mixed import _Walk
+
+from wave_walk_cases import KNOWN, _fail, _history, chain, truncated
 
 pytestmark = pytest.mark.gpu
-
-KNOWN = {"domain-a", "domain-b", "parent-domain"}
 
 
 @pytest.fixture(scope="module")
@@ -34,54 +34,6 @@ def engine():
 def _oracle():
     from oracle import oracle
     return oracle
-
-
-def _history(k: _Walk, w: int) -> WorkflowHistory:
-    return WorkflowHistory(batches=k.batches, domain_failover_version=1, workflow_id=f"wf-{w}",
-                           run_id=det_uuid("run", w), request_id=det_uuid("req", w),
-                           branch_id=det_uuid("branch", w), now_ns=BASE_TS + 10 ** 15 + w)
-
-
-def _activity(k: _Walk, aid: str):
-    """[DecisionTaskCompleted, ActivityTaskScheduled] [ActivityTaskStarted] [ActivityTaskCompleted,
-    DecisionTaskScheduled] [DecisionTaskStarted]: one round of the activity chain (6 events)."""
-    done = k.ev(ET.DecisionTaskCompleted, scheduled_event_id=k.dec_sched, started_event_id=k.dec_started,
-                binary_checksum="bin-0")
-    sched = k.ev(ET.ActivityTaskScheduled, activity_id=aid, domain="", schedule_to_start_timeout_seconds=60,
-                 schedule_to_close_timeout_seconds=600, start_to_close_timeout_seconds=300,
-                 heartbeat_timeout_seconds=0, retry_policy=None)
-    k.emit([done, sched])
-    k.emit([k.ev(ET.ActivityTaskStarted, scheduled_event_id=sched.id, request_id=det_uuid(k.w, "a", sched.id))])
-    k.emit([k.ev(ET.ActivityTaskCompleted, scheduled_event_id=sched.id), k.sched_decision()])
-    k.emit([k.start_decision()])
-
-
-def chain(w: int, activities: int, seed: int = 1) -> _Walk:
-    """The activity-chain workflow (synth.activity_chain_template): 5 + 6 * activities events."""
-    k = _Walk(random.Random(seed * 100003 + w), w, False, ["domain-a"])
-    k.start()
-    k.emit([k.start_decision()])
-    for a in range(activities):
-        _activity(k, str(a))
-    k.emit([k.ev(ET.DecisionTaskCompleted, scheduled_event_id=k.dec_sched, started_event_id=k.dec_started,
-                 binary_checksum="bin-0"), k.ev(ET.WorkflowExecutionCompleted)])
-    return k
-
-
-def truncated(k: _Walk, n: int):
-    """The first n events of the walk, batch structure kept (the last batch may be cut short)."""
-    out, left = [], n
-    for b in k.batches:
-        if left <= 0:
-            break
-        out.append(b[:left])
-        left -= len(b)
-    k.batches = out
-    return k
-
-
-def event_at(k: _Walk, step: int):
-    return [e for b in k.batches for e in b][step]
 
 
 def replay_with_flags(engine, batch):
@@ -140,20 +92,6 @@ def test_ragged_wave(engine):
     ib = _ragged(engine, long_part + short + [0] * 4 + [3 - (i % 4) for i in range(209 - 64)], 8)
     per_wave = [set(int(c) for c in ib.wf["ev_count"][g:g + 64]) for g in range(0, 209, 64)]
     assert per_wave[1] == {3, 2} and per_wave[2] == {2, 1, 0} and per_wave[3] == {0}
-
-
-def _fail(k: _Walk, step: int, kind: str):
-    e = event_at(k, step)
-    if kind == "id":
-        e.id = max(1, e.id - 1)           # event ID not increasing
-    elif kind == "version":
-        e.version -= 1                    # lower version than the version history's last item
-    elif kind == "type":
-        e.event_type = 99                 # unknown event type
-    elif kind == "activity":
-        assert e.event_type == ET.ActivityTaskStarted
-        e.attrs["scheduled_event_id"] = 424242   # no such pending activity
-    return k
 
 
 def test_failures_inside_a_lockstep_wave(engine):
