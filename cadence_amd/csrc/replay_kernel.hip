@@ -3,14 +3,18 @@
 // One lane replays one workflow: every workflow is an independent event-sourced state machine, so
 // a wavefront advances 64 workflows in lock step.
 //
-// Two table policies share one state-machine body (replay_body<P>):
-//   * LdsTables  (fast path, wave-interleaved layout): the pending activity / timer / child /
-//     request-cancel / signal maps and the reset-point keys are indexed in LDS ([slot][lane] SoA,
-//     bank-conflict free).  Every lookup, the per-batch timer epilogue and the checksum's sorted ID
-//     lists are served from LDS; the HBM rows of the output tables are written (never read) during
-//     replay and compacted once at the end.  Group-uniform bases live in SGPRs.  A workflow whose
-//     live set outgrows its LDS slots stops with CRR_INTERNAL_RETRY and is replayed again by
-//   * GlobalTables (any layout, unbounded): the same maps as slot tables in the HBM output rows.
+// Five table policies share one state-machine body (replay_body<P>).  Each holds the pending activity /
+// timer / child / request-cancel / signal maps and the reset-point keys; a workflow whose live set outgrows
+// a bounded policy stops with CRR_INTERNAL_RETRY and is replayed again by a larger one.
+//   * LdsTables      lane per workflow, [slot][lane] tables in LDS: replay_lds_small_kernel, replay_lds_kernel,
+//                    the retry pass's lane list (replay_retry_kernel)
+//   * CompactTables  lane per workflow, packed LDS slots sized per tier: replay_compact1/2/3_kernel
+//   * GlobalTables   lane per workflow, slot tables in the HBM output rows (any layout, unbounded):
+//                    replay_global_kernel, replay_wide_kernel, the retry pass's last resort, checksum_kernel
+//   * WaveRegTables  wavefront per workflow, search state in registers, rows in an LDS arena: the wave-tail
+//                    blocks of replay_lds*_kernel, replay_tail_kernel, replay_big_kernel, replay_retry_kernel
+//   * WaveHbmTables  wavefront per workflow over the HBM output rows (unbounded; continues a loaded state):
+//                    what replay_tail_kernel<., true>, replay_big_kernel and replay_retry_kernel fall back to
 //
 // The column loads of step s+1 are issued before step s is processed (software pipeline).  The
 // checksum streams the thriftrw payload through a slicing-by-8 CRC32 whose tables sit in LDS.
@@ -28,29 +32,12 @@
 #include <utility>
 
 #include "cadence_replay.h"
+#include "replay_kernels.h"
 
 // Checksums: the LdsTables kernels (config 2's) keep their CRC tables in LDS; the compact tiers and
 // the tail kernel, whose occupancy is LDS-limited, read the same tables from constant memory
 // (kCrcGlobal).  The compact tiers write reset-point rows to HBM at push and keep only their keys in LDS.
 // (Experiment variants measured and not kept are described in DESIGN.md §4; they are not in this source.)
-#ifndef CRR_LDS_ACT
-#define CRR_LDS_ACT 2
-#endif
-#ifndef CRR_LDS_TIMER
-#define CRR_LDS_TIMER 2
-#endif
-#ifndef CRR_LDS_CHILD
-#define CRR_LDS_CHILD 1
-#endif
-#ifndef CRR_LDS_RC
-#define CRR_LDS_RC 1
-#endif
-#ifndef CRR_LDS_SIG
-#define CRR_LDS_SIG 1
-#endif
-#ifndef CRR_LDS_RP
-#define CRR_LDS_RP 2
-#endif
 
 namespace crr {
 
@@ -837,7 +824,7 @@ struct Tier {
   static constexpr int LANES = LANES_;  // threads of the block that share the arena
 };
 using SmallTier = Tier<1, 1, 1, 1, 1, 1>;
-using LargeTier = Tier<CRR_LDS_ACT, CRR_LDS_TIMER, CRR_LDS_CHILD, CRR_LDS_RC, CRR_LDS_SIG, CRR_LDS_RP>;
+using LargeTier = Tier<2, 2, 1, 1, 1, 2>;
 // retry pass, lane per workflow, one wavefront per block (67 KB arena: 2 blocks/CU)
 using HugeTier = Tier<8, 8, 4, 4, 4, 8, 64>;
 #define CRR_TIER_SLOTS                                                                      \
@@ -1357,7 +1344,7 @@ struct CompactTables {
   bool have_id0 = false;
   bool retried = false;
   // a map changed since its last batch epilogue; an unchanged map would select the same, already
-  // created, timer again (a no-op), so its epilogue is skipped (as WaveTables)
+  // created, timer again (a no-op), so its epilogue is skipped (as WaveHbmTables)
   bool dirty_act = false, dirty_timer = false;
 
   __device__ __forceinline__ void init(Arena* arena, const crr_inputs* inputs, i64 begin, i32 n_events = 0) {
@@ -2033,13 +2020,13 @@ struct CompactTables {
 };
 
 // ===================================================================================================
-// WaveTables: one wavefront replays one long history (length bucketing).  The
-// state machine runs wave-uniform (scalar registers); the pending maps are full rows that the 64
-// lanes search in parallel (one ballot per 64 slots), the per-batch timer candidates are built in
-// parallel (shuffle argmin) and the live rows are ordered in parallel at the end.  Row storage:
-//   * LdsRows: a per-wave LDS arena (fast path, fused into the lane kernel's launch); a live set
-//     that outgrows it stops with CRR_INTERNAL_RETRY and is replayed again with
-//   * HbmRows: the workflow's own output rows in HBM (bounded only by the host's capacities).
+// The wavefront path: one wavefront replays one long history (length bucketing).  The
+// state machine runs wave-uniform (scalar registers); the 64 lanes search a pending map in parallel
+// (one ballot per 64 slots), build the per-batch timer candidates in parallel (wave argmin) and order
+// the live rows in parallel at the end.  Two table policies:
+//   * WaveRegTables: rows in a per-wave LDS arena (WaveArena), their search state in registers; a live
+//     set that outgrows the arena stops with CRR_INTERNAL_RETRY and is replayed again, last with
+//   * WaveHbmTables: the workflow's own output rows in HBM (bounded only by the host's capacities).
 // ===================================================================================================
 template <int NA, int NT, int NC, int NR, int NS, int NP>
 struct WaveArena {
@@ -2064,40 +2051,41 @@ __device__ __forceinline__ void wave_sync_global() {  // ... and its global-memo
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
+// lane l's (wave-uniform l) value of a per-lane register, wave-uniform: v_readlane into scalar registers
+__device__ __forceinline__ u32 lane_u32(u32 v, i32 l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ i64 readlane_i64(i64 v, i32 l) {
+  const u32 lo = lane_u32((u32)(u64)v, l), hi = lane_u32((u32)((u64)v >> 32), l);
+  return (i64)(((u64)hi << 32) | lo);
+}
+// minimum over the 64 lanes (all active), uniform: DPP steps inside each row of 16, then the
+// row broadcasts of 15 / 31 (lane 63 ends with the wave minimum) -- VALU moves, no LDS crossbar
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ i64 dpp_min_step(i64 v) {
+  const u32 lo = (u32)(u64)v, hi = (u32)((u64)v >> 32);
+  const u32 olo = (u32)__builtin_amdgcn_update_dpp((int)lo, (int)lo, CTRL, ROW_MASK, 0xF, false);
+  const u32 ohi = (u32)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, ROW_MASK, 0xF, false);
+  const i64 o = (i64)(((u64)ohi << 32) | olo);
+  return o < v ? o : v;
+}
+__device__ __forceinline__ i64 wave_min_i64(i64 v) {
+  v = dpp_min_step<0x128, 0xF>(v);  // row_ror:8
+  v = dpp_min_step<0x124, 0xF>(v);  // row_ror:4
+  v = dpp_min_step<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
+  v = dpp_min_step<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
+  v = dpp_min_step<0x142, 0xA>(v);  // row_bcast:15 -> rows 1, 3
+  v = dpp_min_step<0x143, 0xC>(v);  // row_bcast:31 -> rows 2, 3
+  return readlane_i64(v, 63);
+}
+// a wave argmin over more candidate lanes than this first narrows them to the ones holding the minimum
+// time (wave_min_i64); up to this many go straight to the scalar pass
+constexpr i32 kWaveMinScalar = 2;
 
-template <class ARENA, int LIST>
-struct LdsRows {
-  static constexpr bool kLds = true;
-  static constexpr int kList = LIST;  // scratch list a workflow that outgrows the arena is handed to
-  static constexpr i32 A = ARENA::A, T = ARENA::T, C = ARENA::C, R = ARENA::R, S = ARENA::S, P = ARENA::P;
-  // WaveTables::act_cand_store keeps two words per activity slot in ids[] until finalize
-  static_assert(A + T + C + R + S >= 2 * A, "ids[] too small for the activity candidate cache");
-  ARENA* M;
-  __device__ __forceinline__ crr_activity_row& act(i32 j) const { return M->act[j]; }
-  __device__ __forceinline__ crr_timer_row& timer(i32 j) const { return M->timer[j]; }
-  __device__ __forceinline__ crr_child_row& child(i32 j) const { return M->child[j]; }
-  __device__ __forceinline__ crr_initiated_row& rc(i32 j) const { return M->rc[j]; }
-  __device__ __forceinline__ crr_initiated_row& sig(i32 j) const { return M->sig[j]; }
-  __device__ __forceinline__ crr_reset_point_row& rp(i32 j) const { return M->rp[j]; }
-};
-struct HbmRows {
-  static constexpr bool kLds = false;
-  static constexpr int kList = -1;    // never outgrown
-  static constexpr i32 A = 0x3fffffff, T = A, C = A, R = A, S = A, P = A;
-  Geo G;
-  __device__ __forceinline__ crr_activity_row& act(i32 j) const { return *G.act(j); }
-  __device__ __forceinline__ crr_timer_row& timer(i32 j) const { return *G.timer(j); }
-  __device__ __forceinline__ crr_child_row& child(i32 j) const { return *G.child(j); }
-  __device__ __forceinline__ crr_initiated_row& rc(i32 j) const { return *G.rc(j); }
-  __device__ __forceinline__ crr_initiated_row& sig(i32 j) const { return *G.sig(j); }
-  __device__ __forceinline__ crr_reset_point_row& rp(i32 j) const { return *G.rp(j); }
-};
-
-template <class ST>
-struct WaveTables {
-  static constexpr bool kResumable = !ST::kLds;  // HbmRows continue a loaded state in place
+// The pending maps as the workflow's own HBM output rows, never outgrown: the rows are searched where
+// they lie, so a loaded state is continued in place.
+struct WaveHbmTables {
+  static constexpr bool kResumable = true;
   __device__ __forceinline__ static bool fits(i64) { return true; }
-  ST S;
+  Geo G;  // the workflow's rows (replay_wave_item sets it)
   i32 lane;
   i32 hw_act = 0, hw_timer = 0, hw_child = 0, hw_rc = 0, hw_sig = 0;
   bool retried = false;
@@ -2107,17 +2095,18 @@ struct WaveTables {
 
   __device__ __forceinline__ void init() { lane = (i32)(threadIdx.x & 63); }
 
-  // HbmRows ownership: slot j is only ever written and searched by lane j % 64, so every HBM read
-  // follows that lane's own writes (single work-item ordering, no fences); a uniform read of a
-  // row field takes the owner lane's value.  LDS rows are shared by the whole wave.
-  // Every lane stores a shared LDS row itself: with one writer lane the compiler may forward the old
-  // value to the others' later loads (per-thread reasoning: they never stored), and the lanes'
-  // copies of the wave-uniform state diverge (measured: corrupted exec rows).
-  __device__ __forceinline__ bool own(i32 j) const { return ST::kLds || lane == (j & 63); }
-  __device__ __forceinline__ u32 bcast(i32 j, u32 v) const {
-    if constexpr (ST::kLds) return v;
-    else return __builtin_amdgcn_readlane(v, j & 63);
-  }
+  __device__ __forceinline__ crr_activity_row& act(i32 j) const { return *G.act(j); }
+  __device__ __forceinline__ crr_timer_row& timer(i32 j) const { return *G.timer(j); }
+  __device__ __forceinline__ crr_child_row& child(i32 j) const { return *G.child(j); }
+  __device__ __forceinline__ crr_initiated_row& rc(i32 j) const { return *G.rc(j); }
+  __device__ __forceinline__ crr_initiated_row& sig(i32 j) const { return *G.sig(j); }
+  __device__ __forceinline__ crr_reset_point_row& rp(i32 j) const { return *G.rp(j); }
+
+  // Ownership: slot j is only ever written and searched by lane j % 64, so every HBM read follows
+  // that lane's own writes (single work-item ordering, no fences); a uniform read of a row field
+  // takes the owner lane's value.
+  __device__ __forceinline__ bool own(i32 j) const { return lane == (j & 63); }
+  __device__ __forceinline__ u32 bcast(i32 j, u32 v) const { return __builtin_amdgcn_readlane(v, j & 63); }
 
   // first slot j < hw with pred(row j) (uniform), -1 if none.  The bound is made scalar (the compiler
   // cannot tell that the high-water marks are wave-uniform: a loop over a VGPR bound is compiled as a
@@ -2134,23 +2123,27 @@ struct WaveTables {
     }
     return -1;
   }
-  // lowest free slot (GlobalTables::free_slot semantics); CAPACITY when `cap` rows are live,
-  // INTERNAL_RETRY when the row storage is full first.  Returns the slot or a negative status.
+  // slot indices stay below this: a map that reached it would stop with CRR_INTERNAL_RETRY.  The host's
+  // capacities are far smaller, so CAPACITY always comes first; the compiler cannot know that, and dropping
+  // the two checks (take, rp_push) changes the code of every kernel that holds this policy
+  static constexpr i32 kSlotLimit = 0x3fffffff;
+  // lowest free slot (GlobalTables::free_slot semantics); CAPACITY when `cap` rows are live.
+  // Returns the slot or a negative status.
   template <class Row>
-  __device__ __forceinline__ i32 take(Row row, i32& hw, i32 store_cap, i32 cap) const {
+  __device__ __forceinline__ i32 take(Row row, i32& hw, i32 cap) const {
     i32 j = find(row, hw, [](const auto& r) { return !(r.flags & CRR_ROW_LIVE); });
     if (j < 0) j = hw;
     if (j >= cap) return -CRR_ERR_CAPACITY;
-    if (j >= store_cap) return -CRR_INTERNAL_RETRY;
+    if (j >= kSlotLimit) return -CRR_INTERNAL_RETRY;
     if (j == hw) ++hw;
     return j;
   }
-  __device__ __forceinline__ auto A_() const { return [this](i32 j) -> crr_activity_row& { return S.act(j); }; }
-  __device__ __forceinline__ auto T_() const { return [this](i32 j) -> crr_timer_row& { return S.timer(j); }; }
-  __device__ __forceinline__ auto C_() const { return [this](i32 j) -> crr_child_row& { return S.child(j); }; }
-  __device__ __forceinline__ auto R_() const { return [this](i32 j) -> crr_initiated_row& { return S.rc(j); }; }
-  __device__ __forceinline__ auto S_() const { return [this](i32 j) -> crr_initiated_row& { return S.sig(j); }; }
-  __device__ __forceinline__ auto P_() const { return [this](i32 j) -> crr_reset_point_row& { return S.rp(j); }; }
+  __device__ __forceinline__ auto A_() const { return [this](i32 j) -> crr_activity_row& { return act(j); }; }
+  __device__ __forceinline__ auto T_() const { return [this](i32 j) -> crr_timer_row& { return timer(j); }; }
+  __device__ __forceinline__ auto C_() const { return [this](i32 j) -> crr_child_row& { return child(j); }; }
+  __device__ __forceinline__ auto R_() const { return [this](i32 j) -> crr_initiated_row& { return rc(j); }; }
+  __device__ __forceinline__ auto S_() const { return [this](i32 j) -> crr_initiated_row& { return sig(j); }; }
+  __device__ __forceinline__ auto P_() const { return [this](i32 j) -> crr_reset_point_row& { return rp(j); }; }
 
   // predicates with both fields read (bitwise &): a short-circuit && puts the second load behind a branch
   // and its own wait
@@ -2172,27 +2165,12 @@ struct WaveTables {
     return find(row, hw, [&](const auto& r) { return ((r.flags & CRR_ROW_LIVE) != 0) & (r.initiated_id == id); });
   }
 
-  // LdsRows: each activity's earliest timer candidate (timer_sequence.go:269-381 over its own timeouts),
-  // kept current by what changes it -- the insert, the start, the epilogue's created mark, RefreshTasks
-  // -- in the arena's ids[] (unused until finalize): the epilogue then reads one candidate per row
-  // instead of recomputing every row's.  ids[j]: the time; ids[A + j]: 1 | type << 8 | created << 16.
-  __device__ __forceinline__ void act_cand_store(i32 j, const crr_activity_row& r) {
-    if constexpr (ST::kLds) {
-      BestTimer B;
-      activity_candidates(B, j, r.schedule_id, r.scheduled_time, r.started_id != CRR_EMPTY_EVENT_ID, r.started_time,
-                          max(r.started_time, r.last_heartbeat_time), r.schedule_to_start, r.schedule_to_close,
-                          r.start_to_close, r.heartbeat, (u32)r.timer_task_status);
-      S.M->ids[j] = B.t;
-      S.M->ids[ST::A + j] = B.have ? (i64)(1u | ((u32)B.y << 8) | ((B.created ? 1u : 0u) << 16)) : 0;
-    }
-  }
   __device__ __forceinline__ int act_insert(Lane& L, const Geo& G, const crr_activity_row& row) {
     const i32 m = find_act_mapped(row.key);
-    const i32 j = take(A_(), hw_act, ST::A, G.act_cap);
+    const i32 j = take(A_(), hw_act, G.act_cap);
     if (j < 0) return -j;
-    if (m >= 0 && own(m)) S.act(m).flags &= ~CRR_ROW_MAPPED;
-    if (own(j)) S.act(j) = row;
-    act_cand_store(j, row);
+    if (m >= 0 && own(m)) act(m).flags &= ~CRR_ROW_MAPPED;
+    if (own(j)) act(j) = row;
     ++L.n_act;
     dirty_act = true;
     return CRR_OK;
@@ -2202,34 +2180,33 @@ struct WaveTables {
     if (j < 0) return CRR_ERR_MISSING_ACTIVITY_INFO;
     dirty_act = true;
     if (own(j)) {
-      crr_activity_row& r = S.act(j);
+      crr_activity_row& r = act(j);
       r.version = ver;
       r.started_id = id;
       r.started_src = s;
       r.started_time = ts;
       r.last_heartbeat_time = ts;
-      act_cand_store(j, r);
     }
     return CRR_OK;
   }
   __device__ __forceinline__ void act_delete(Lane& L, const Geo& G, i64 sched) {
     const i32 j = find_act_by_id(sched);
     if (j < 0) { ++L.inconsistencies; return; }
-    const u32 f = bcast(j, S.act(j).flags);
-    const u32 key = bcast(j, S.act(j).key);
-    if (own(j)) S.act(j).flags = f & ~(CRR_ROW_LIVE | CRR_ROW_MAPPED);
+    const u32 f = bcast(j, act(j).flags);
+    const u32 key = bcast(j, act(j).key);
+    if (own(j)) act(j).flags = f & ~(CRR_ROW_LIVE | CRR_ROW_MAPPED);
     --L.n_act;
     dirty_act = true;
     if (f & CRR_ROW_MAPPED) return;
     const i32 m = find_act_mapped(key);
-    if (m >= 0) { if (own(m)) S.act(m).flags &= ~CRR_ROW_MAPPED; }
+    if (m >= 0) { if (own(m)) act(m).flags &= ~CRR_ROW_MAPPED; }
     else ++L.inconsistencies;
   }
   __device__ __forceinline__ void act_cancel(Lane& L, const Geo& G, u32 key, i64 id, i64 ver, i32 /*s*/) {
     const i32 j = find_act_mapped(key);
     if (j < 0) return;
     if (own(j)) {
-      crr_activity_row& r = S.act(j);
+      crr_activity_row& r = act(j);
       r.version = ver;
       r.flags |= CRR_ROW_CANCEL_REQUESTED;
       r.cancel_request_id = id;
@@ -2238,25 +2215,25 @@ struct WaveTables {
   __device__ __forceinline__ int timer_start(Lane& L, const Geo& G, const crr_timer_row& row) {
     i32 j = find_timer(row.key);
     if (j < 0) {
-      j = take(T_(), hw_timer, ST::T, G.timer_cap);
+      j = take(T_(), hw_timer, G.timer_cap);
       if (j < 0) return -j;
       ++L.n_timer;
     }
-    if (own(j)) S.timer(j) = row;
+    if (own(j)) timer(j) = row;
     dirty_timer = true;
     return CRR_OK;
   }
   __device__ __forceinline__ void timer_delete(Lane& L, const Geo& G, u32 key) {
     const i32 j = find_timer(key);
     if (j < 0) { ++L.inconsistencies; return; }
-    if (own(j)) S.timer(j).flags = 0;
+    if (own(j)) timer(j).flags = 0;
     --L.n_timer;
     dirty_timer = true;
   }
   __device__ __forceinline__ int child_insert(Lane& L, const Geo& G, const crr_child_row& row) {
-    const i32 j = take(C_(), hw_child, ST::C, G.child_cap);
+    const i32 j = take(C_(), hw_child, G.child_cap);
     if (j < 0) return -j;
-    if (own(j)) S.child(j) = row;
+    if (own(j)) child(j) = row;
     ++L.n_child;
     return CRR_OK;
   }
@@ -2264,23 +2241,23 @@ struct WaveTables {
     const i32 j = find_initiated(C_(), hw_child, init);
     if (j < 0) return CRR_ERR_MISSING_CHILD_INFO;
     if (own(j)) {
-      S.child(j).started_id = id;
-      S.child(j).started_src = s;
+      child(j).started_id = id;
+      child(j).started_src = s;
     }
     return CRR_OK;
   }
   __device__ __forceinline__ void child_delete(Lane& L, const Geo& G, i64 init) {
     const i32 j = find_initiated(C_(), hw_child, init);
     if (j < 0) { ++L.inconsistencies; return; }
-    if (own(j)) S.child(j).flags = 0;
+    if (own(j)) child(j).flags = 0;
     --L.n_child;
   }
   __device__ __forceinline__ int init_insert(Lane& L, const Geo& G, bool is_rc, const crr_initiated_row& row) {
-    const i32 j = is_rc ? take(R_(), hw_rc, ST::R, G.rc_cap) : take(S_(), hw_sig, ST::S, G.sig_cap);
+    const i32 j = is_rc ? take(R_(), hw_rc, G.rc_cap) : take(S_(), hw_sig, G.sig_cap);
     if (j < 0) return -j;
     if (own(j)) {
-      if (is_rc) S.rc(j) = row;
-      else S.sig(j) = row;
+      if (is_rc) rc(j) = row;
+      else sig(j) = row;
     }
     if (is_rc) ++L.n_rc; else ++L.n_sig;
     return CRR_OK;
@@ -2289,40 +2266,38 @@ struct WaveTables {
     const i32 j = is_rc ? find_initiated(R_(), hw_rc, init) : find_initiated(S_(), hw_sig, init);
     if (j < 0) { ++L.inconsistencies; return; }
     if (own(j)) {
-      if (is_rc) S.rc(j).flags = 0;
-      else S.sig(j).flags = 0;
+      if (is_rc) rc(j).flags = 0;
+      else sig(j).flags = 0;
     }
     if (is_rc) --L.n_rc; else --L.n_sig;
   }
-  // Load over HbmRows (GlobalTables::load): lane j % 64 writes row j; the fields read across lanes (key,
-  // ScheduleID) are not written here
+  // Load (GlobalTables::load): lane j % 64 writes row j; the fields read across lanes (key, ScheduleID)
+  // are not written here
   __device__ __forceinline__ void load(Lane& L, const Geo& G) {
     hw_act = L.n_act; hw_timer = L.n_timer; hw_child = L.n_child; hw_rc = L.n_rc; hw_sig = L.n_sig;
     dirty_act = dirty_timer = true;
-    if constexpr (kResumable) {
-      for (i32 j = lane; j < hw_act; j += 64) {
-        crr_activity_row& r = S.act(j);
-        const u32 key = r.key;
-        const i64 sid = r.schedule_id;
-        bool mapped = true;
-        for (i32 k = 0; k < hw_act; ++k) {
-          const crr_activity_row& o = S.act(k);
-          if (k != j && o.key == key && o.schedule_id > sid) mapped = false;
-        }
-        r.flags = (r.flags & ~CRR_ROW_MAPPED) | CRR_ROW_LIVE | (mapped ? CRR_ROW_MAPPED : 0u);
+    for (i32 j = lane; j < hw_act; j += 64) {
+      crr_activity_row& r = act(j);
+      const u32 key = r.key;
+      const i64 sid = r.schedule_id;
+      bool mapped = true;
+      for (i32 k = 0; k < hw_act; ++k) {
+        const crr_activity_row& o = act(k);
+        if (k != j && o.key == key && o.schedule_id > sid) mapped = false;
       }
-      for (i32 j = lane; j < hw_timer; j += 64) S.timer(j).flags |= CRR_ROW_LIVE;
-      for (i32 j = lane; j < hw_child; j += 64) S.child(j).flags |= CRR_ROW_LIVE;
-      for (i32 j = lane; j < hw_rc; j += 64) S.rc(j).flags |= CRR_ROW_LIVE;
-      for (i32 j = lane; j < hw_sig; j += 64) S.sig(j).flags |= CRR_ROW_LIVE;
-      wave_sync_global();
+      r.flags = (r.flags & ~CRR_ROW_MAPPED) | CRR_ROW_LIVE | (mapped ? CRR_ROW_MAPPED : 0u);
     }
+    for (i32 j = lane; j < hw_timer; j += 64) timer(j).flags |= CRR_ROW_LIVE;
+    for (i32 j = lane; j < hw_child; j += 64) child(j).flags |= CRR_ROW_LIVE;
+    for (i32 j = lane; j < hw_rc; j += 64) rc(j).flags |= CRR_ROW_LIVE;
+    for (i32 j = lane; j < hw_sig; j += 64) sig(j).flags |= CRR_ROW_LIVE;
+    wave_sync_global();
   }
   __device__ __forceinline__ void rp_reset(Lane& L) { L.n_rp = 0; }
   __device__ __forceinline__ int rp_push(Lane& L, const Geo& G, const crr_reset_point_row& row) {
     if (L.n_rp >= G.rp_cap) return CRR_ERR_CAPACITY;
-    if (L.n_rp >= ST::P) return CRR_INTERNAL_RETRY;
-    if (own(L.n_rp)) S.rp(L.n_rp) = row;
+    if (L.n_rp >= kSlotLimit) return CRR_INTERNAL_RETRY;
+    if (own(L.n_rp)) rp(L.n_rp) = row;
     ++L.n_rp;
     return CRR_OK;
   }
@@ -2330,41 +2305,14 @@ struct WaveTables {
     return find(P_(), L.n_rp, [&](const crr_reset_point_row& r) { return r.key == key; }) >= 0;
   }
 
-#ifndef CRR_WAVE_MIN_SCALAR
-#define CRR_WAVE_MIN_SCALAR 2
-#endif
   // argmin of the per-lane candidates across the wavefront (keys are unique: (time, eventID, type)):
   // a scalar pass with readlane over the candidate lanes -- all of them when few, else only those
-  // holding the minimum timestamp (found with a shuffle tree over the timestamp alone).
-  __device__ __forceinline__ static i64 readlane64(i64 v, i32 l) {
-    const u32 lo = __builtin_amdgcn_readlane((u32)(u64)v, l);
-    const u32 hi = __builtin_amdgcn_readlane((u32)((u64)v >> 32), l);
-    return (i64)(((u64)hi << 32) | lo);
-  }
-  // minimum over the 64 lanes (all active), uniform: DPP steps inside each row of 16, then the
-  // row broadcasts of 15 / 31 (lane 63 ends with the wave minimum) -- VALU moves, no LDS crossbar
-  template <int CTRL, int ROW_MASK>
-  __device__ __forceinline__ static i64 dpp_min_step(i64 v) {
-    const u32 lo = (u32)(u64)v, hi = (u32)((u64)v >> 32);
-    const u32 olo = (u32)__builtin_amdgcn_update_dpp((int)lo, (int)lo, CTRL, ROW_MASK, 0xF, false);
-    const u32 ohi = (u32)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, ROW_MASK, 0xF, false);
-    const i64 o = (i64)(((u64)ohi << 32) | olo);
-    return o < v ? o : v;
-  }
-  __device__ __forceinline__ static i64 wave_min_i64(i64 v) {
-    v = dpp_min_step<0x128, 0xF>(v);  // row_ror:8
-    v = dpp_min_step<0x124, 0xF>(v);  // row_ror:4
-    v = dpp_min_step<0x4E, 0xF>(v);   // quad_perm [2,3,0,1]
-    v = dpp_min_step<0xB1, 0xF>(v);   // quad_perm [1,0,3,2]
-    v = dpp_min_step<0x142, 0xA>(v);  // row_bcast:15 -> rows 1, 3
-    v = dpp_min_step<0x143, 0xC>(v);  // row_bcast:31 -> rows 2, 3
-    return readlane64(v, 63);
-  }
+  // holding the minimum timestamp (found with a wave minimum over the timestamp alone).
   __device__ __forceinline__ static void wave_min(BestTimer& B) {
     u64 m = __builtin_amdgcn_ballot_w64(B.have);
-    if (__builtin_popcountll(m) > CRR_WAVE_MIN_SCALAR) {
-      // many candidates: reduce the timestamp alone (two crossbar shuffles per level), then keep only
-      // the lanes holding the minimum (almost always one) for the scalar pass below
+    if (__builtin_popcountll(m) > kWaveMinScalar) {
+      // many candidates: reduce the timestamp alone, then keep only the lanes holding the minimum
+      // (almost always one) for the scalar pass below
       const i64 t = wave_min_i64(B.have ? B.t : (i64)0x7fffffffffffffffLL);
       m = __builtin_amdgcn_ballot_w64(B.have && B.t == t);
     }
@@ -2373,7 +2321,7 @@ struct WaveTables {
       while (m) {
         const i32 l = (i32)__builtin_ctzll(m);
         m &= m - 1;
-        const i64 t = readlane64(B.t, l), e = readlane64(B.e, l);
+        const i64 t = readlane_i64(B.t, l), e = readlane_i64(B.e, l);
         const i32 y = (i32)__builtin_amdgcn_readlane((u32)B.y, l);
         if (!R.have || seq_less(t, e, y, R.t, R.e, R.y)) {
           R.have = true; R.t = t; R.e = e; R.y = y;
@@ -2390,29 +2338,20 @@ struct WaveTables {
       BestTimer B;
       const i32 hwa = uniform32(hw_act);
       for (i32 j = lane; j < hwa; j += 64) {
-        const crr_activity_row& r = S.act(j);
-        if constexpr (ST::kLds) {  // the row's flags and ID and its cached candidate, read together
-          const u32 fl = r.flags;
-          const i64 sid = r.schedule_id;
-          const i64 w = S.M->ids[ST::A + j];
-          const i64 ct = S.M->ids[j];
-          if ((fl & CRR_ROW_LIVE) && (w & 1)) B.offer(ct, sid, (i32)((w >> 8) & 0xff), j, ((w >> 16) & 1) != 0);
-        } else {
-          if (!(r.flags & CRR_ROW_LIVE)) continue;
-          activity_candidates(B, j, r.schedule_id, r.scheduled_time, r.started_id != CRR_EMPTY_EVENT_ID, r.started_time,
-                              max(r.started_time, r.last_heartbeat_time),
-                              r.schedule_to_start, r.schedule_to_close, r.start_to_close, r.heartbeat,
-                              (u32)r.timer_task_status);
-        }
+        const crr_activity_row& r = act(j);
+        if (!(r.flags & CRR_ROW_LIVE)) continue;
+        activity_candidates(B, j, r.schedule_id, r.scheduled_time, r.started_id != CRR_EMPTY_EVENT_ID, r.started_time,
+                            max(r.started_time, r.last_heartbeat_time),
+                            r.schedule_to_start, r.schedule_to_close, r.start_to_close, r.heartbeat,
+                            (u32)r.timer_task_status);
       }
       wave_min(B);
       i32 attempt = 0;
       if (B.have && !B.created && own(B.j)) {
-        crr_activity_row& r = S.act(B.j);
+        crr_activity_row& r = act(B.j);
         r.timer_task_status |= timer_mask(B.y);
         if (B.y == CRR_TIMEOUT_HEARTBEAT) r.last_hb_timeout_vis_s = unix_seconds(B.t);
         attempt = r.attempt;
-        if constexpr (ST::kLds) S.M->ids[ST::A + B.j] |= (i64)1 << 16;  // the row's earliest is now created
       }
       if (B.have && !B.created) K.add(L, G, CRR_TASK_ACTIVITY_TIMEOUT, B.y, L.current_version, B.t, B.e, (i32)bcast(B.j, (u32)attempt), -1);
     }
@@ -2421,14 +2360,14 @@ struct WaveTables {
       BestTimer B;
       const i32 hwt = uniform32(hw_timer);
       for (i32 j = lane; j < hwt; j += 64) {
-        const crr_timer_row& r = S.timer(j);
+        const crr_timer_row& r = timer(j);
         const u32 fl = r.flags;
         const i64 ex = r.expiry_time, sid = r.started_id;
         const i32 ts = r.task_status;
         if (fl & CRR_ROW_LIVE) B.offer(ex, sid, 0, j, ts == CRR_TIMER_TASK_STATUS_CREATED);
       }
       wave_min(B);
-      if (B.have && !B.created && own(B.j)) S.timer(B.j).task_status = CRR_TIMER_TASK_STATUS_CREATED;
+      if (B.have && !B.created && own(B.j)) timer(B.j).task_status = CRR_TIMER_TASK_STATUS_CREATED;
       if (B.have && !B.created) K.add(L, G, CRR_TASK_USER_TIMER, 0, L.current_version, B.t, B.e, 0, -1);
     }
     dirty_timer = false;
@@ -2437,33 +2376,14 @@ struct WaveTables {
   // RefreshTasks' state effects (mutable_state_task_refresher.go:278-365); each lane clears the slots
   // the epilogue's candidate loop reads with the same lane, so no cross-lane ordering is needed
   __device__ __forceinline__ void refresh(Lane& L, const Geo& G) {
-    for (i32 j = lane; j < hw_act; j += 64) {
-      S.act(j).timer_task_status = CRR_TIMER_TASK_STATUS_NONE;
-      if constexpr (ST::kLds) S.M->ids[ST::A + j] &= ~((i64)1 << 16);
-    }
-    if constexpr (ST::kLds) wave_sync_lds();
-    for (i32 j = lane; j < hw_timer; j += 64) S.timer(j).task_status = CRR_TIMER_TASK_STATUS_NONE;
+    for (i32 j = lane; j < hw_act; j += 64) act(j).timer_task_status = CRR_TIMER_TASK_STATUS_NONE;
+    for (i32 j = lane; j < hw_timer; j += 64) timer(j).task_status = CRR_TIMER_TASK_STATUS_NONE;
     dirty_act = dirty_timer = true;
     epilogue(L, G, TaskSink{false, false});
   }
 
-  // LdsRows: live rows -> HBM slots 0..n-1 in event-ID order (rank = number of smaller live IDs);
-  // the sorted IDs -> ids[] for the checksum lists
-  template <class R, class Row, class IdOf>
-  __device__ __forceinline__ void scatter(Row row, i32 hw, i64* ids, R* (Geo::*dst)(i32) const, const Geo& G,
-                                          IdOf id_of) const {
-    for (i32 j = lane; j < hw; j += 64) {
-      const R& r = row(j);
-      if (!(r.flags & CRR_ROW_LIVE)) continue;
-      const i64 id = id_of(r);
-      i32 rank = 0;
-      for (i32 k = 0; k < hw; ++k) rank += ((row(k).flags & CRR_ROW_LIVE) && id_of(row(k)) < id) ? 1 : 0;
-      *(G.*dst)(rank) = r;
-      ids[rank] = id;
-    }
-  }
-  // HbmRows: in-place selection sort of the live rows into slots 0..n-1 (parallel argmin per slot,
-  // rows swapped one 8-byte word per lane)
+  // in-place selection sort of the live rows into slots 0..n-1 (parallel argmin per slot, rows swapped
+  // one 8-byte word per lane)
   template <class R, class Row, class IdOf>
   __device__ __forceinline__ void sort_in_place(Row row, i32 hw, i32 n, IdOf id_of) const {
     for (i32 i = 0; i < n; ++i) {
@@ -2498,49 +2418,19 @@ struct WaveTables {
     wave_sync_global();
   }
   __device__ __forceinline__ void finalize(Lane& L, const Geo& G) {
-    if constexpr (ST::kLds) {
-      i64* ids = S.M->ids;
-      constexpr i32 oT = ST::A, oC = oT + ST::T, oR = oC + ST::C, oS = oR + ST::R;
-      scatter<crr_activity_row>(A_(), hw_act, ids, &Geo::act, G, [](const crr_activity_row& r) { return r.schedule_id; });
-      scatter<crr_timer_row>(T_(), hw_timer, ids + oT, &Geo::timer, G, [](const crr_timer_row& r) { return r.started_id; });
-      scatter<crr_child_row>(C_(), hw_child, ids + oC, &Geo::child, G, [](const crr_child_row& r) { return r.initiated_id; });
-      scatter<crr_initiated_row>(R_(), hw_rc, ids + oR, &Geo::rc, G, [](const crr_initiated_row& r) { return r.initiated_id; });
-      scatter<crr_initiated_row>(S_(), hw_sig, ids + oS, &Geo::sig, G, [](const crr_initiated_row& r) { return r.initiated_id; });
-      for (i32 i = lane; i < L.n_rp; i += 64) *G.rp(i) = S.rp(i);
-      wave_sync_lds();
-    } else {
-      sort_in_place<crr_activity_row>(A_(), hw_act, L.n_act, [](const crr_activity_row& r) { return r.schedule_id; });
-      sort_in_place<crr_timer_row>(T_(), hw_timer, L.n_timer, [](const crr_timer_row& r) { return r.started_id; });
-      sort_in_place<crr_child_row>(C_(), hw_child, L.n_child, [](const crr_child_row& r) { return r.initiated_id; });
-      sort_in_place<crr_initiated_row>(R_(), hw_rc, L.n_rc, [](const crr_initiated_row& r) { return r.initiated_id; });
-      sort_in_place<crr_initiated_row>(S_(), hw_sig, L.n_sig, [](const crr_initiated_row& r) { return r.initiated_id; });
-    }
+    sort_in_place<crr_activity_row>(A_(), hw_act, L.n_act, [](const crr_activity_row& r) { return r.schedule_id; });
+    sort_in_place<crr_timer_row>(T_(), hw_timer, L.n_timer, [](const crr_timer_row& r) { return r.started_id; });
+    sort_in_place<crr_child_row>(C_(), hw_child, L.n_child, [](const crr_child_row& r) { return r.initiated_id; });
+    sort_in_place<crr_initiated_row>(R_(), hw_rc, L.n_rc, [](const crr_initiated_row& r) { return r.initiated_id; });
+    sort_in_place<crr_initiated_row>(S_(), hw_sig, L.n_sig, [](const crr_initiated_row& r) { return r.initiated_id; });
   }
-  __device__ __forceinline__ i64 act_id(const Geo& G, i32 i) const {
-    if constexpr (ST::kLds) return S.M->ids[i]; else return G.act(i)->schedule_id;
-  }
-  __device__ __forceinline__ i64 timer_id(const Geo& G, i32 i) const {
-    if constexpr (ST::kLds) return S.M->ids[ST::A + i]; else return G.timer(i)->started_id;
-  }
-  __device__ __forceinline__ i64 child_id(const Geo& G, i32 i) const {
-    if constexpr (ST::kLds) return S.M->ids[ST::A + ST::T + i]; else return G.child(i)->initiated_id;
-  }
-  __device__ __forceinline__ i64 rc_id(const Geo& G, i32 i) const {
-    if constexpr (ST::kLds) return S.M->ids[ST::A + ST::T + ST::C + i]; else return G.rc(i)->initiated_id;
-  }
-  __device__ __forceinline__ i64 sig_id(const Geo& G, i32 i) const {
-    if constexpr (ST::kLds) return S.M->ids[ST::A + ST::T + ST::C + ST::R + i]; else return G.sig(i)->initiated_id;
-  }
-  // kList < 0: the caller replays the workflow again itself (replay_retry_kernel)
-  __device__ __forceinline__ void retry_push(const crr_inputs& in, const crr_outputs& out, u32 w) {
-    retried = true;
-    if constexpr (ST::kList >= 0) {
-      if (lane == 0) {
-        const u32 k = atomicAdd(out.scratch + ST::kList, 1u);
-        out.scratch[retry_slot(in, ST::kList, k)] = w;
-      }
-    }
-  }
+  __device__ __forceinline__ i64 act_id(const Geo& G, i32 i) const { return G.act(i)->schedule_id; }
+  __device__ __forceinline__ i64 timer_id(const Geo& G, i32 i) const { return G.timer(i)->started_id; }
+  __device__ __forceinline__ i64 child_id(const Geo& G, i32 i) const { return G.child(i)->initiated_id; }
+  __device__ __forceinline__ i64 rc_id(const Geo& G, i32 i) const { return G.rc(i)->initiated_id; }
+  __device__ __forceinline__ i64 sig_id(const Geo& G, i32 i) const { return G.sig(i)->initiated_id; }
+  // nothing replays a workflow after this policy: a stop with CRR_INTERNAL_RETRY is only recorded
+  __device__ __forceinline__ void retry_push(const crr_inputs&, const crr_outputs&, u32) { retried = true; }
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -2548,29 +2438,19 @@ struct WaveTables {
 // in registers.  Slot j of a map is register j / 64 of lane j % 64: each slot's key / ID, its flags and
 // (activities, timers) the epilogue's candidate.  A search is a compare and a ballot per 64 slots, a free
 // slot the first lane with a clear LIVE bit, and a batch epilogue a wave minimum over registers: no LDS
-// round trip on the walk's critical path (WaveTables<LdsRows> searched 112-B LDS rows: 2-3 dependent
-// LDS round trips per map operation).  The rows themselves stay in the LDS arena (at finalize lane j % 64
+// round trip on the walk's critical path (searching the 112-B LDS rows themselves took 2-3 dependent LDS
+// round trips per map operation).  The rows stay in the LDS arena M (at finalize lane j % 64
 // reads row j), and the flags / timer-task bits the mirror holds are patched in when finalize writes them
-// to HBM.  Every lane stores a row it changes (the same values to the same LDS address): a store by its
-// owner lane alone is a branch on the lane, and the compiler then takes the whole walk -- the loop and
-// everything it carries -- as divergent (exec-mask regions, its state in VGPRs).  Nothing in the walk
+// to HBM.  A workflow that outgrows the arena is handed to scratch list LIST; LIST < 0: the caller replays
+// it again itself.  Every lane stores a row it changes (the same values to the same LDS address): a store
+// by its owner lane alone is a branch on the lane, and the compiler then takes the whole walk -- the loop
+// and everything it carries -- as divergent (exec-mask regions, its state in VGPRs); with one writer lane
+// the compiler may also forward the old value to the other lanes' later loads.  Nothing in the walk
 // branches on a per-lane value.
 // fl words: bits 0-7 the row's CRR_ROW_* flags; activities: bit 8 a candidate cached, 9-11 its timeout
 // type, 12 it is created, 16-19 TimerTaskStatus; timers: bit 8 TimerTaskStatusCreated.
-#ifndef CRR_WAVE_REG
-#define CRR_WAVE_REG 1
-#endif
-// register sets past the high-water mark skipped by scalar branches (big arenas: 5 activity registers)
-#ifndef CRR_WAVE_SKIP
-#define CRR_WAVE_SKIP 0
-#endif
 constexpr u32 kMirLive = CRR_ROW_LIVE, kMirMapped = CRR_ROW_MAPPED;
 constexpr u32 kMirHave = 1u << 8, kMirCreated = 1u << 12, kMirTimerCreated = 1u << 8;
-__device__ __forceinline__ i64 readlane_i64(i64 v, i32 l) {
-  const u32 lo = __builtin_amdgcn_readlane((u32)(u64)v, l);
-  const u32 hi = __builtin_amdgcn_readlane((u32)((u64)v >> 32), l);
-  return (i64)(((u64)hi << 32) | lo);
-}
 // f(integral_constant<int, 0>), ..., f(integral_constant<int, N - 1>): the register arrays below are only ever
 // indexed by such constants, so they stay in registers (a loop index -- even one the unroller removes later --
 // leaves them in scratch memory)
@@ -2594,7 +2474,7 @@ struct WaveRegTables {
   i32 lane;
   i32 hw_act = 0, hw_timer = 0, hw_child = 0, hw_rc = 0, hw_sig = 0;  // slots ever used (wave-uniform)
   bool retried = false;
-  bool dirty_act = false, dirty_timer = false;  // as WaveTables
+  bool dirty_act = false, dirty_timer = false;  // as WaveHbmTables
   i64 a_id[NA], a_ct[NA];   // ScheduleID; the cached earliest timer candidate's time
   u32 a_key[NA], a_fl[NA];
   u32 t_key[NT], t_fl[NT];
@@ -2622,11 +2502,7 @@ struct WaveRegTables {
   __device__ __forceinline__ static V get(const V (&a)[N], i32 j) {
     const i32 jk = j >> 6;
     V x = a[0];
-#if CRR_WAVE_SKIP
-    each<N>([&](auto k) { if constexpr (k > 0) { if (jk == k) x = a[k]; } });
-#else
     each<N>([&](auto k) { if constexpr (k > 0) x = jk == k ? a[k] : x; });
-#endif
     if constexpr (sizeof(V) == 8) return (V)readlane_i64((i64)x, j & 63);
     else return (V)__builtin_amdgcn_readlane((u32)x, j & 63);
   }
@@ -2634,21 +2510,13 @@ struct WaveRegTables {
   __device__ __forceinline__ void put(V (&a)[N], i32 j, V v) const {
     const i32 jk = j >> 6;
     const bool me = lane == (j & 63);
-#if CRR_WAVE_SKIP
-    each<N>([&](auto k) { if (jk == k) a[k] = me ? v : a[k]; });
-#else
     each<N>([&](auto k) { a[k] = (me & (jk == k)) ? v : a[k]; });
-#endif
   }
   template <int N>
   __device__ __forceinline__ void set_bits(u32 (&a)[N], i32 j, u32 set, u32 clear) const {
     const i32 jk = j >> 6;
     const bool me = lane == (j & 63);
-#if CRR_WAVE_SKIP
-    each<N>([&](auto k) { if (jk == k) a[k] = me ? ((a[k] & ~clear) | set) : a[k]; });
-#else
     each<N>([&](auto k) { a[k] = (me & (jk == k)) ? ((a[k] & ~clear) | set) : a[k]; });
-#endif
   }
   // first slot (< hw) whose lane-predicate holds, -1 if none.  Every register's ballot is taken (no early
   // exit: a loop that can leave early may stay a loop, and index the arrays dynamically)
@@ -2658,15 +2526,8 @@ struct WaveRegTables {
     i32 r = -1;
     each<N>([&](auto kk) {
       constexpr int k = N - 1 - (int)kk;
-#if CRR_WAVE_SKIP
-      if (64 * k < n) {
-        const u64 m = __builtin_amdgcn_ballot_w64(pred(std::integral_constant<int, k>{}));
-        r = m ? 64 * k + (i32)__builtin_ctzll(m) : r;
-      }
-#else
       const u64 m = __builtin_amdgcn_ballot_w64(pred(std::integral_constant<int, k>{})) & (64 * k < n ? ~0ull : 0ull);
       r = m ? 64 * k + (i32)__builtin_ctzll(m) : r;
-#endif
     });
     return r;
   }
@@ -2675,18 +2536,10 @@ struct WaveRegTables {
   template <int N>
   __device__ __forceinline__ static i32 take(const u32 (&fl)[N], i32& hw, i32 store_cap, i32 cap) {
     i32 j = N * 64;
-    const i32 h = uniform32(hw);
     each<N>([&](auto kk) {
       constexpr int k = N - 1 - (int)kk;
-#if CRR_WAVE_SKIP
-      if (64 * k <= h) {  // the first free slot is at most hw
-        const u64 m = __builtin_amdgcn_ballot_w64(!(fl[k] & kMirLive));
-        j = m ? 64 * k + (i32)__builtin_ctzll(m) : j;
-      }
-#else
       const u64 m = __builtin_amdgcn_ballot_w64(!(fl[k] & kMirLive));
       j = m ? 64 * k + (i32)__builtin_ctzll(m) : j;
-#endif
     });
     if (j >= cap) return -CRR_ERR_CAPACITY;
     if (j >= store_cap) return -CRR_INTERNAL_RETRY;
@@ -2868,10 +2721,10 @@ struct WaveRegTables {
     if (cnt == 0) return -1;
     i32 best = -1;
     i64 bt = 0, be = 0;
-    if (cnt > CRR_WAVE_MIN_SCALAR) {
+    if (cnt > kWaveMinScalar) {
       i64 v = 0x7fffffffffffffffLL;
       each<N>([&](auto k) { v = (ok[k] && t[k] < v) ? t[k] : v; });
-      const i64 wm = WaveTables<HbmRows>::wave_min_i64(v);
+      const i64 wm = wave_min_i64(v);
       each<N>([&](auto k) { m[k] = __builtin_amdgcn_ballot_w64(ok[k] && t[k] == wm); });
     }
     each<N>([&](auto k) {
@@ -2977,19 +2830,6 @@ struct WaveRegTables {
     }
   }
 };
-
-// The wavefront path's LDS-arena tables (CRR_WAVE_REG=0: the round-5 WaveTables over LDS rows, for A/B)
-#if CRR_WAVE_REG
-template <class ARENA, int LIST>
-using WaveLds = WaveRegTables<ARENA, LIST>;
-template <class ARENA, int LIST>
-__device__ __forceinline__ void bind_arena(WaveRegTables<ARENA, LIST>& T, ARENA* a) { T.M = a; }
-#else
-template <class ARENA, int LIST>
-using WaveLds = WaveTables<LdsRows<ARENA, LIST>>;
-template <class ARENA, int LIST>
-__device__ __forceinline__ void bind_arena(WaveTables<LdsRows<ARENA, LIST>>& T, ARENA* a) { T.S.M = a; }
-#endif
 
 // ---------------------------------------------------------------------------------------------------
 // Event sources.  LaneSource: one workflow per lane, the 8 column loads of step s+1 are issued before
@@ -3159,15 +2999,10 @@ struct WaveLaneSource : LaneSource {
 // one chunk ahead).  Per chunk the version-history prologue of all 64 events runs lane-parallel
 // (replay_body); the transitions then walk the chunk one event at a time and read each field out of
 // its lane only where they use it (WaveEv): a MarkerRecorded reads nothing, a DecisionTaskCompleted
-// two fields, instead of every event broadcasting all seven.
-//   CRR_WAVE_FIELDS 0: __shfl (LDS crossbar) into VGPRs; 1: v_readlane into SGPRs; 2: v_readlane then a
-//   VGPR copy.  Round 3 (config 4, alternating A/B on one box): 13.4 / 13.9 / 13.9 ms, against 15.7 ms for the
-//   per-event prologue with every field broadcast.  Round 5, once the slot searches and the chunk bounds were
-//   scalar: 1 is the fastest (config 4 6.05 -> 5.61 ms, the 256 longest runs alone 4.55 -> 4.24 ms; 2: no
-//   gain): with the fields scalar the transitions' branches are scalar branches, not exec-masked regions.
-#ifndef CRR_WAVE_FIELDS
-#define CRR_WAVE_FIELDS 1
-#endif
+// two fields, instead of every event broadcasting all seven.  A field is read with v_readlane into scalar
+// registers (lane_u32 / readlane_i64): with the fields scalar the transitions' branches are scalar branches,
+// not exec-masked regions (round 5, once the slot searches and the chunk bounds were scalar: config 4
+// 6.05 -> 5.61 ms, the 256 longest runs alone 4.55 -> 4.24 ms; the __shfl alternatives are in DESIGN.md §4).
 struct WaveSource {
   const crr_events& E;
   i64 begin, st;
@@ -3196,25 +3031,6 @@ struct WaveSource {
     if ((c + 1) * 64 < n) nxt = load_chunk(c + 1);
   }
 };
-// lane l's value of a per-lane register, wave-uniform (CRR_WAVE_FIELDS above)
-__device__ __forceinline__ u32 lane_u32(u32 v, i32 l) {
-#if CRR_WAVE_FIELDS == 0
-  return (u32)__shfl((int)v, l, 64);
-#else
-  const u32 r = __builtin_amdgcn_readlane(v, l);
-#if CRR_WAVE_FIELDS == 2
-  u32 o;
-  asm("v_mov_b32 %0, %1" : "=v"(o) : "s"(r));
-  return o;
-#else
-  return r;
-#endif
-#endif
-}
-__device__ __forceinline__ i64 lane_i64(i64 v, i32 l) {
-  const u32 lo = lane_u32((u32)(u64)v, l), hi = lane_u32((u32)((u64)v >> 32), l);
-  return (i64)(((u64)hi << 32) | lo);
-}
 // ActivityTaskScheduled's side record (the fields the transitions read), gathered lane-parallel for the
 // whole chunk before the walk: the walk's insert reads it out of its lane instead of waiting on a
 // dependent HBM load per insert
@@ -3237,11 +3053,11 @@ struct WaveEv {
     a.domain_status = (i32)lane_u32((u32)sp->dom, l);
     return a;
   }
-  __device__ __forceinline__ i64 id() const { return lane_i64(C.id_, l); }
-  __device__ __forceinline__ i64 ver() const { return lane_i64(C.ver_, l); }
-  __device__ __forceinline__ i64 ts() const { return lane_i64(C.ts_, l); }
+  __device__ __forceinline__ i64 id() const { return readlane_i64(C.id_, l); }
+  __device__ __forceinline__ i64 ver() const { return readlane_i64(C.ver_, l); }
+  __device__ __forceinline__ i64 ts() const { return readlane_i64(C.ts_, l); }
   __device__ __forceinline__ i64 task() const { return 0; }
-  __device__ __forceinline__ i64 ref() const { return lane_i64(C.ref_, l); }
+  __device__ __forceinline__ i64 ref() const { return readlane_i64(C.ref_, l); }
   __device__ __forceinline__ u32 key() const { return lane_u32(C.key_, l); }
   __device__ __forceinline__ i32 aux() const { return (i32)lane_u32((u32)C.aux_, l); }
 };
@@ -4103,8 +3919,8 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
 #define WAVE_VH_AFTER(k)                                                                          \
       do {                                                                                        \
         L.vh_n = vh_n0 + __builtin_popcountll(gm & (~0ull >> (63 - (k))));                        \
-        L.vh_last_id = lane_i64(C.id_, (k));                                                      \
-        L.vh_last_ver = lane_i64(C.ver_, (k));                                                    \
+        L.vh_last_id = readlane_i64(C.id_, (k));                                                      \
+        L.vh_last_ver = readlane_i64(C.ver_, (k));                                                    \
       } while (0)
       const u32 tl = C.et & CRR_ETYPE_MASK;
       const bool live = valid && lane < lim;
@@ -4191,12 +4007,12 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
           if (et & CRR_ETYPE_BATCH_FIRST) batch_first_id = ev.id();  // firstEvent := history[0] (:101)
           bfid = batch_first_id;
           // :112 UpdateCurrentVersion: a closed workflow keeps its version history's last version
-          L.current_version = L.state == CRR_STATE_COMPLETED ? lane_i64(pver, j) : ev.ver();
+          L.current_version = L.state == CRR_STATE_COMPLETED ? readlane_i64(pver, j) : ev.ver();
           last_task_step = s;  // :129 SetLastEventTaskID(event.TaskID): read once, after the loop
         } else if (((1ull << (et & CRR_ETYPE_MASK)) & kBatchIdTypes) != 0) {
           // only the inserts record their batch's first event ID
           const i32 bf = last_in(BF & le(j));
-          if (bf >= 0) bfid = lane_i64(C.id_, bf);
+          if (bf >= 0) bfid = readlane_i64(C.id_, bf);
         }
         if (!fast || ((OPS >> j) & 1)) {
           // the status is wave-uniform (every lane replays the same workflow), and read as such: a status the
@@ -4237,18 +4053,18 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
           const i32 tp = (i32)__builtin_amdgcn_readlane(tl, p);
           auto att_at = [&](i32 x) -> i64 {  // a failed / timed-out decision's attempt
             const i32 v = last_in((DS | DT | DC) & le(x - 1));
-            const i64 base = v < 0 ? L.decision_attempt : ((DS >> v) & 1) ? lane_i64(C.ref_, v) : 0;
+            const i64 base = v < 0 ? L.decision_attempt : ((DS >> v) & 1) ? readlane_i64(C.ref_, v) : 0;
             return base + __builtin_popcountll(DM & le(x) & ~le(v));
           };
           i64 nv, ns, nst = CRR_EMPTY_EVENT_ID, natt = 0, nsts = 0, nscts = 0, nots = 0;
           i32 nreq = CRR_SRC_EMPTY_UUID, nto = 0;
           if (tp == CRR_EV_DECISION_TASK_SCHEDULED) {  // :129-166
-            nv = lane_i64(C.ver_, p); ns = lane_i64(C.id_, p); nto = (i32)lane_u32((u32)C.aux_, p);
-            natt = lane_i64(C.ref_, p); nscts = lane_i64(C.ts_, p); nots = nscts;
+            nv = readlane_i64(C.ver_, p); ns = readlane_i64(C.id_, p); nto = (i32)lane_u32((u32)C.aux_, p);
+            natt = readlane_i64(C.ref_, p); nscts = readlane_i64(C.ts_, p); nots = nscts;
           } else if (tp == CRR_EV_DECISION_TASK_STARTED || tp == CRR_EV_DECISION_TASK_COMPLETED) {
             // the original scheduled time: the last Scheduled (its time) or failure (0) before it
             const i32 r = last_in((DM & ~(DT | DC)) & le(p - 1));
-            nots = r < 0 ? L.decision_orig_scheduled_ts : ((DS >> r) & 1) ? lane_i64(C.ts_, r) : 0;
+            nots = r < 0 ? L.decision_orig_scheduled_ts : ((DS >> r) & 1) ? readlane_i64(C.ts_, r) : 0;
             if (tp == CRR_EV_DECISION_TASK_STARTED) {  // :199-242
               // the timeout and scheduled time: the last decision event before it that sets them
               const i32 q = last_in(DM & ~DT & le(p - 1));
@@ -4257,7 +4073,7 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
                 nscts = L.decision_scheduled_ts;
               } else if ((DS >> q) & 1) {
                 nto = (i32)lane_u32((u32)C.aux_, q);
-                nscts = lane_i64(C.ts_, q);
+                nscts = readlane_i64(C.ts_, q);
               } else if ((DC >> q) & 1) {
                 nto = 0;
                 nscts = 0;
@@ -4265,8 +4081,8 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
                 nto = att_at(q) != 0 ? L.decision_start_to_close : 0;
                 nscts = now_ns;
               }
-              nv = lane_i64(C.ver_, p); ns = lane_i64(C.ref_, p); nst = lane_i64(C.id_, p);
-              nreq = c0 + p + L.src_base; nsts = lane_i64(C.ts_, p);
+              nv = readlane_i64(C.ver_, p); ns = readlane_i64(C.ref_, p); nst = readlane_i64(C.id_, p);
+              nreq = c0 + p + L.src_base; nsts = readlane_i64(C.ts_, p);
             } else {  // DeleteDecision (:244-249, :827-838)
               nv = CRR_EMPTY_VERSION; ns = CRR_EMPTY_EVENT_ID;
             }
@@ -4274,15 +4090,15 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
             natt = att_at(p);
             const bool tr = natt != 0;
             const i32 b = last_in(BL & le(p - 1));
-            nv = tr ? lane_i64(C.ver_, p) : (i64)CRR_EMPTY_VERSION;
-            ns = !tr ? (i64)CRR_EMPTY_EVENT_ID : b < 0 ? L.next_event_id : lane_i64(C.id_, b) + 1;
+            nv = tr ? readlane_i64(C.ver_, p) : (i64)CRR_EMPTY_VERSION;
+            ns = !tr ? (i64)CRR_EMPTY_EVENT_ID : b < 0 ? L.next_event_id : readlane_i64(C.id_, b) + 1;
             nto = tr ? L.decision_start_to_close : 0;
             nscts = now_ns;
           }
           update_decision(L, nv, ns, nst, nreq, nto, natt, nsts, nscts, nots);
         }
         const i32 q = last_in(DC);
-        if (q >= 0) L.last_processed_event = lane_i64(C.ref_, q);
+        if (q >= 0) L.last_processed_event = readlane_i64(C.ref_, q);
         if (DS & E) {  // UpdateWorkflowStateCloseStatus(Running, None) (:185-208)
           L.state = CRR_STATE_RUNNING;
           L.close_status = CRR_CLOSE_NONE;
@@ -4294,14 +4110,14 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
         const i32 b = last_in(BL & E);
         if (b >= 0) {  // :642-643
           const i32 bf = last_in(BF & le(b));
-          L.last_first_event_id = bf < 0 ? batch_first_id : lane_i64(C.id_, bf);
-          L.next_event_id = lane_i64(C.id_, b) + 1;
+          L.last_first_event_id = bf < 0 ? batch_first_id : readlane_i64(C.id_, bf);
+          L.next_event_id = readlane_i64(C.id_, b) + 1;
         }
         const i32 f = last_in(BF & E);
-        if (f >= 0) batch_first_id = lane_i64(C.id_, f);
+        if (f >= 0) batch_first_id = readlane_i64(C.id_, f);
         const i32 k = wfail >= 0 ? wfail : stop < lim ? stop : lim - 1;  // the last event whose prologue ran
         if (k >= 0) {
-          L.current_version = lane_i64(C.ver_, k);
+          L.current_version = readlane_i64(C.ver_, k);
           last_task_step = c0 + k;
         }
         if (wfail < 0 && stop < lim) {  // DecisionTaskStarted without its decision (:210-228)
@@ -4316,7 +4132,7 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
       if (lim > 0) WAVE_VH_AFTER(lim - 1);
       if (lim < cnt) {  // event c0 + lim fails its prologue; a version-history error follows UpdateCurrentVersion
         if (__builtin_amdgcn_readlane((u32)rc0, lim) == 0)
-          L.current_version = L.state == CRR_STATE_COMPLETED ? lane_i64(pver, lim) : lane_i64(C.ver_, lim);
+          L.current_version = L.state == CRR_STATE_COMPLETED ? readlane_i64(pver, lim) : readlane_i64(C.ver_, lim);
         FAIL((i32)__builtin_amdgcn_readlane((u32)prc, lim), c0 + lim);
       }
 #undef WAVE_VH_AFTER
@@ -4540,10 +4356,28 @@ __device__ __forceinline__ i64 wf_stride(const crr_inputs& in, u32 w) {
   return ((in.flags & CRR_IN_WAVE_TAIL) && w >= in.wave_begin) ? 1 : (i64)in.stride;
 }
 
-// LDS arena of a block: the lane-per-workflow [slot][lane] tables or 4 per-wave row arenas.
-#ifndef CRR_SMALL_CRC  // the lane kernels' CRC tables: 0 built in LDS per block, 1 copied into LDS, 2 none
-#define CRR_SMALL_CRC 0
+// Register budgets of the kernels below as waves per SIMD (__launch_bounds__' second argument), overridable
+// with -D for an occupancy A/B (tools/build_variant.py); each kernel's comment says why its value.
+#ifndef CRR_SMALL_WAVES_PER_EU
+#define CRR_SMALL_WAVES_PER_EU 3
 #endif
+#ifndef CRR_WIDE_WAVES_PER_EU
+#define CRR_WIDE_WAVES_PER_EU 2
+#endif
+#ifndef CRR_COMPACT1_WAVES_PER_EU
+#define CRR_COMPACT1_WAVES_PER_EU 2
+#endif
+#ifndef CRR_COMPACT1_RESUME_WAVES_PER_EU
+#define CRR_COMPACT1_RESUME_WAVES_PER_EU 2
+#endif
+#ifndef CRR_COMPACT2_WAVES_PER_EU
+#define CRR_COMPACT2_WAVES_PER_EU 2
+#endif
+#ifndef CRR_TAIL_WAVES_PER_EU
+#define CRR_TAIL_WAVES_PER_EU 3
+#endif
+
+// LDS arena of a block: the lane-per-workflow [slot][lane] tables or 4 per-wave row arenas.
 template <class TIER> struct WaveTier;
 template <> struct WaveTier<SmallTier> { using Arena = WaveArena<40, 32, 16, 8, 8, 24>; };
 template <> struct WaveTier<LargeTier> { using Arena = WaveArena<64, 48, 24, 16, 16, 32>; };
@@ -4582,22 +4416,8 @@ __device__ __forceinline__ void replay_lds(const crr_inputs& in, const crr_outpu
     ev_count0 = wfp->ev_count;
     wf_flags = wfp->flags;
   }
-#if CRR_SMALL_CRC == 2
-  const u32* crc_tables = kCrcGlobal.v;  // gathers through the L1
-#else
-  __shared__ u32 crc_tables[8 * 256];
-#if CRR_SMALL_CRC == 1
-  {  // a copy of the constant-memory tables
-    const uint4* src = reinterpret_cast<const uint4*>(kCrcGlobal.v);
-    uint4* dst = reinterpret_cast<uint4*>(crc_tables);
-#pragma unroll
-    for (int i = 0; i < 8 * 256 / 4 / kBlock; ++i) dst[i * kBlock + threadIdx.x] = src[i * kBlock + threadIdx.x];
-    __syncthreads();
-  }
-#else
+  __shared__ u32 crc_tables[8 * 256];  // the lane kernels' CRC tables are built in LDS per block
   build_crc_tables<kBlock>(crc_tables);
-#endif
-#endif
   __shared__ BlockArena<TIER> arena;
   if (WAVE_TAIL && !lane_block) {
     const u32 wv = (u32)uniform32((i32)(threadIdx.x >> 6));
@@ -4607,8 +4427,8 @@ __device__ __forceinline__ void replay_lds(const crr_inputs& in, const crr_outpu
     if (((wtp->flags & CRR_WF_FLAG_NEW_RUN) != 0) != (phase == 0)) return;
     Geo GT;
     load_geo(GT, wtp, out, 1);
-    WaveLds<typename WaveTier<TIER>::Arena, 1> T;  // outgrown: the retry pass's wave list
-    bind_arena(T, &arena.wave[wv]);
+    WaveRegTables<typename WaveTier<TIER>::Arena, 1> T;  // outgrown: the retry pass's wave list
+    T.M = &arena.wave[wv];
     T.init();
 
     WaveSource S(in.ev, wtp->ev_begin, 1, wtp->ev_count);
@@ -4635,10 +4455,7 @@ __device__ __forceinline__ void replay_lds(const crr_inputs& in, const crr_outpu
     replay_body<EMIT>(in, out, w, wfp, G, T, S, crc_tables, nullptr, &D);
   }
 }
-template <bool WAVE_TAIL, bool EMIT, bool LANES = false>
-#ifndef CRR_SMALL_WAVES_PER_EU
-#define CRR_SMALL_WAVES_PER_EU 3
-#endif
+template <bool WAVE_TAIL, bool EMIT, bool LANES>
 __global__ void __launch_bounds__(kBlock, EMIT ? 2 : CRR_SMALL_WAVES_PER_EU) replay_lds_small_kernel(crr_inputs in, crr_outputs out, int phase, u32 lo, u32 hi) {
   Digest D;
   replay_lds<SmallTier, WAVE_TAIL, EMIT, LANES>(in, out, phase, lo, hi, D);
@@ -4702,10 +4519,7 @@ using BigArena = WaveArena<320, 160, 96, 64, 64, 64>;  // the retry pass's wave 
 // replay_big_kernel's: the big segment holds the histories whose live sets the host expects past the wave
 // tail's arena (64 activities, 48 timers) -- in config 4 they peak at 65-71 -- so two registers per map
 // (WaveRegTables) cover them; a live set past this is replayed again over the 320-slot arena, then HBM rows
-#ifndef CRR_BIG_ARENA
-#define CRR_BIG_ARENA 128, 128, 64, 64, 64, 64
-#endif
-using BigSegArena = WaveArena<CRR_BIG_ARENA>;
+using BigSegArena = WaveArena<128, 128, 64, 64, 64, 64>;
 template <class TT, bool EMIT = true>
 __device__ __forceinline__ void replay_wave_item(const crr_inputs& in, const crr_outputs& out, int phase, u32 w,
                                                  TT& T, const u32* crc_tables, Digest& D) {
@@ -4714,9 +4528,8 @@ __device__ __forceinline__ void replay_wave_item(const crr_inputs& in, const crr
   const i64 st = wf_stride(in, w);
   Geo G;
   load_geo(G, wfp, out, st);
-  if constexpr (std::is_same<TT, WaveTables<HbmRows>>::value) T.S.G = G;
+  if constexpr (std::is_same<TT, WaveHbmTables>::value) T.G = G;
   T.init();
-  T.hw_act = T.hw_timer = T.hw_child = T.hw_rc = T.hw_sig = 0;
   WaveSource S(in.ev, wfp->ev_begin, st, wfp->ev_count);
   replay_body<EMIT, TT, WaveSource>(in, out, w, wfp, G, T, S, crc_tables, nullptr, &D);
 }
@@ -4742,9 +4555,6 @@ __device__ __forceinline__ void replay_lane_item(const crr_inputs& in, const crr
 // outgrow the compact tiers, and loaded states (CRR_WF_FLAG_RESUME: continued in place over their rows).
 // Lane per workflow over the workflows' own HBM rows (GlobalTables: no LDS, so the occupancy is the
 // register-limited one; interleaved rows keep slot j of a group one coalesced run).
-#ifndef CRR_WIDE_WAVES_PER_EU
-#define CRR_WIDE_WAVES_PER_EU 2
-#endif
 __device__ __forceinline__ void replay_wide(const crr_inputs& in, const crr_outputs& out, int phase, u32 lo, u32 hi,
                                             const u32* crc_tables, Digest& D) {
   const u32 w = lo + blockIdx.x * kBlock + threadIdx.x;
@@ -4791,12 +4601,10 @@ using CompactTier3 = CTier<12, 8, 6, 4, 4, 8, 64>;
 // tables in LDS, A/B on one box; their occupancy is register-limited, so the 8 KB costs no waves).  Tier 3's
 // resume kernel (one wave per SIMD, few workflows) does better on the constant-memory tables: 0.885 ->
 // 0.85 ms with tiers 1-2 only (round 4, A/B)
-#ifndef CRR_COMPACT_LDS_CRC_MASK  // bit k: tier k+1's resume instantiation (bit 3+k: its fresh one)
-#define CRR_COMPACT_LDS_CRC_MASK 3
-#endif
+constexpr u32 kCompactLdsCrcMask = 3;  // bit k: tier k+1's resume instantiation (bit 3+k: its fresh one)
 template <int TIER_NO, bool RESUME>
 struct CompactLdsCrc {
-  static constexpr bool value = ((CRR_COMPACT_LDS_CRC_MASK >> ((TIER_NO - 1) + (RESUME ? 0 : 3))) & 1) != 0;
+  static constexpr bool value = ((kCompactLdsCrcMask >> ((TIER_NO - 1) + (RESUME ? 0 : 3))) & 1) != 0;
 };
 template <class TIER, bool EMIT, bool RESUME, int TIER_NO>
 __device__ __forceinline__ void replay_compact(const crr_inputs& in, const crr_outputs& out, int phase, u32 lo, u32 hi,
@@ -4840,17 +4648,8 @@ __device__ __forceinline__ void replay_compact(const crr_inputs& in, const crr_o
 }
 // register budgets (waves per SIMD): tier 1's 10-KB blocks would fit 15 per CU, but at 3 waves/SIMD (168
 // VGPRs) its loop spills 24 VGPRs (156 B/lane of scratch); at 2 (256 VGPRs) none, and the config-3 shard
-// replays 2.55-2.59 ms against 2.60-2.66 (round 5, alternated A/B on one box); tier 2's 20-KB blocks fit 8
-#ifndef CRR_COMPACT1_WAVES_PER_EU
-#define CRR_COMPACT1_WAVES_PER_EU 2
-#endif
-// the resume instantiation at 2: its loaded-row reads and in-place finalize spill at 168 VGPRs
-#ifndef CRR_COMPACT1_RESUME_WAVES_PER_EU
-#define CRR_COMPACT1_RESUME_WAVES_PER_EU 2
-#endif
-#ifndef CRR_COMPACT2_WAVES_PER_EU
-#define CRR_COMPACT2_WAVES_PER_EU 2
-#endif
+// replays 2.55-2.59 ms against 2.60-2.66 (round 5, alternated A/B on one box); tier 2's 20-KB blocks fit 8.
+// Tier 1's resume instantiation at 2: its loaded-row reads and in-place finalize spill at 168 VGPRs
 template <bool EMIT, bool RESUME>
 __global__ void __launch_bounds__(64, RESUME ? CRR_COMPACT1_RESUME_WAVES_PER_EU : CRR_COMPACT1_WAVES_PER_EU) replay_compact1_kernel(crr_inputs in, crr_outputs out, int phase, u32 lo, u32 hi) {
   Digest D;
@@ -4902,15 +4701,15 @@ __global__ void __launch_bounds__(64) replay_big_kernel(crr_inputs in, crr_outpu
   Digest D;
   // two registers per map first; a live set past that is replayed again with the retry pass's 320-slot arena
   // (five registers per map), then over the HBM rows
-  WaveLds<BigSegArena, -1> T;
-  bind_arena(T, &arena.seg);
+  WaveRegTables<BigSegArena, -1> T;
+  T.M = &arena.seg;
   replay_wave_item(in, out, phase, w, T, crc_tables, D);
   if (T.retried) {
-    WaveLds<BigArena, -1> T2;
-    bind_arena(T2, &arena.big);
+    WaveRegTables<BigArena, -1> T2;
+    T2.M = &arena.big;
     replay_wave_item(in, out, phase, w, T2, crc_tables, D);
     if (T2.retried) {
-      WaveTables<HbmRows> H;
+      WaveHbmTables H;
       replay_wave_item(in, out, phase, w, H, crc_tables, D);
     }
   }
@@ -4921,9 +4720,6 @@ __global__ void __launch_bounds__(64) replay_big_kernel(crr_inputs in, crr_outpu
 // replayed again over its HBM rows in the same wavefront.  The checksum reads the constant-memory CRC
 // tables: without 8 KB of CRC tables in LDS 13 blocks fit a CU, so with <= 168 VGPRs the tail runs 3
 // waves per SIMD -- 3072 at once, enough for config 4's tail in one round.
-#ifndef CRR_TAIL_WAVES_PER_EU
-#define CRR_TAIL_WAVES_PER_EU 3
-#endif
 // RESUME (a batch holding loaded states, CRR_IN_HAS_RESUME): a workflow the LDS arena cannot hold -- it
 // outgrew it, or resumes a loaded state -- is replayed again over its HBM rows in the same wavefront.
 // Otherwise such a workflow (the host's bounds route the ones expected to outgrow to the big segment) goes
@@ -4949,14 +4745,14 @@ __global__ void __launch_bounds__(64, CRR_TAIL_WAVES_PER_EU) replay_tail_kernel(
   __shared__ WaveTier<LargeTier>::Arena arena;
   const u32 w = lo + blockIdx.x;
   if (w >= hi) return;
-  WaveLds<WaveTier<LargeTier>::Arena, RESUME ? -1 : 1> T;
-  bind_arena(T, &arena);
+  WaveRegTables<WaveTier<LargeTier>::Arena, RESUME ? -1 : 1> T;
+  T.M = &arena;
   Digest D;
   replay_wave_item<decltype(T), EMIT>(in, out, phase, w, T, crc_tables, D);
   if constexpr (RESUME) {
     if (T.retried) {
-      WaveTables<HbmRows> H;
-      replay_wave_item<WaveTables<HbmRows>, EMIT>(in, out, phase, w, H, crc_tables, D);
+      WaveHbmTables H;
+      replay_wave_item<WaveHbmTables, EMIT>(in, out, phase, w, H, crc_tables, D);
     }
   }
   digest_flush(out, D);
@@ -4988,11 +4784,11 @@ __global__ void __launch_bounds__(64) replay_retry_kernel(crr_inputs in, crr_out
   for (u32 i = blockIdx.x; i < n1; i += gridDim.x) {  // 1. long-tail workflows (they run longest)
     const u32 w = (u32)uniform32((i32)out.scratch[retry_slot(in, 1, i)]);
     if (w >= in.n_wf) continue;
-    WaveLds<BigArena, -1> T;
-    bind_arena(T, &arena.wave);
+    WaveRegTables<BigArena, -1> T;
+    T.M = &arena.wave;
     replay_wave_item(in, out, phase, w, T, crc_tables, D);
     if (T.retried) {
-      WaveTables<HbmRows> H;
+      WaveHbmTables H;
       replay_wave_item(in, out, phase, w, H, crc_tables, D);
     }
   }

@@ -1,7 +1,7 @@
 """Profiling aid (not product code): the replay library rebuilt with extra -D switches, for A/B runs on
 one box (tools/prof_kernel.py / tools/prof_longtail.py --lib).
 
-    python tools/build_variant.py NAME [--src=FILE] -DCRR_WAVE_FIELDS=0 [...]   ->  tools/variants/NAME.so
+    python tools/build_variant.py NAME [--src=FILE] -DCRR_TAIL_WAVES_PER_EU=2 [...]   ->  tools/variants/NAME.so
 
 Only replay_kernel.hip (or the --src= file, e.g. ingest_kernel.hip) is recompiled; the other objects come
 from build/ (__graft_entry__.build()).

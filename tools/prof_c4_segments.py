@@ -101,14 +101,7 @@ def main():
                                  "per_map_op": cyc["map_op_visits"] / max(cnts["map_ops"], 1),
                                  "per_epilogue": cyc["epilogues"] / max(cnts["epilogues"], 1),
                                  "per_op": {n: {"count": w[32 + i], "cycles_each": w[16 + i] / max(w[32 + i], 1)}
-                                            for i, n in enumerate(MOPS) if w[32 + i]},
-                                 "wave_tables": {"act_epilogue": {"count": w[56], "cand_loads": w[48] / max(w[56], 1),
-                                                                  "wave_min": w[49] / max(w[56], 1),
-                                                                  "update": w[50] / max(w[56], 1)},
-                                                 "timer_epilogue": {"count": w[57], "cycles_each": w[51] / max(w[57], 1)},
-                                                 "act_insert": {"find_mapped": w[52] / max(w[33], 1),
-                                                                "take": w[53] / max(w[33], 1),
-                                                                "write": w[54] / max(w[33], 1)}}}
+                                            for i, n in enumerate(MOPS) if w[32 + i]}}
         print(json.dumps(line), flush=True)
         del db
         torch.cuda.empty_cache()
