@@ -4137,7 +4137,7 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
       }
 #undef WAVE_VH_AFTER
     }
-  } else
+  } else {
   for (i32 s = 0; s < n_ev; ++s) {
     // one loop exit for the whole prologue: the checks become a select chain (no divergent branch
     // per check), and on success vh_last = (id, ver) in every case (new item, same version, first).
@@ -4148,30 +4148,45 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
     const i32 t = et & CRR_ETYPE_MASK;
     if (et & CRR_ETYPE_BATCH_FIRST) batch_first_id = id;  // firstEvent := history[0] (:101)
     {
-      const bool completed = L.state == CRR_STATE_COMPLETED;
-      const bool first = L.vh_n == 0;
-      const bool grow = !first && ver > L.vh_last_ver;
-      // :98-100 empty batch; :112 UpdateCurrentVersion (mutable_state_builder.go:495-533)
-      i32 rc0 = s == empty_at ? (i32)CRR_ERR_EMPTY_HISTORY : (completed && first) ? (i32)CRR_ERR_VH_EMPTY : 0;
-      if (rc0 == 0) L.current_version = completed ? L.vh_last_ver : ver;
-      // :123-128 AddOrUpdateItem(NewVersionHistoryItem(event.ID, event.Version)) (versionHistory.go:32-46, :193-226)
-      const i32 vh_rc = (id < 0 || (ver < 0 && ver != CRR_EMPTY_VERSION)) ? (i32)CRR_ERR_VH_INVALID_ITEM
-                        : first ? (G.vh_cap < 1 ? (i32)CRR_ERR_CAPACITY : 0)
-                        : ver < L.vh_last_ver ? (i32)CRR_ERR_VH_LOWER_VERSION
-                        : id <= L.vh_last_id ? (i32)CRR_ERR_VH_EVENT_ID_NOT_INCREASING
-                        : (grow && L.vh_n >= G.vh_cap) ? (i32)CRR_ERR_CAPACITY : 0;
-      rc0 = rc0 ? rc0 : vh_rc;
-      if (rc0) FAIL(rc0, s);
-      if (grow) {
-        crr_vh_item* it = G.vh(L.vh_n - 1);
-        it->event_id = L.vh_last_id;
-        it->version = L.vh_last_ver;
+      // The usual event continues its history's last item: a valid (ID, version), the version of the item,
+      // a larger ID, on a workflow that is not closed, in a batch that is not the empty one.  Then nothing
+      // fails, no item is added or closed, and the prologue is current_version = ver, vh_last = (id, ver).
+      // Anything else in any lane -- the first event of a history among them -- sends the wavefront through
+      // the full checks: one ballot, and the select chain and the item write stay out of the common path.
+      const bool usual = (id | ver) >= 0 && ver == L.vh_last_ver && id > L.vh_last_id && L.vh_n != 0 &&
+                         L.state != CRR_STATE_COMPLETED && s != empty_at;
+      i64 cur_ver = ver;
+      if (__builtin_amdgcn_ballot_w64(!usual) != 0) {
+        const bool completed = L.state == CRR_STATE_COMPLETED;
+        const bool first = L.vh_n == 0;
+        const bool grow = !first && ver > L.vh_last_ver;
+        // :98-100 empty batch; :112 UpdateCurrentVersion (mutable_state_builder.go:495-533)
+        i32 rc0 = s == empty_at ? (i32)CRR_ERR_EMPTY_HISTORY : (completed && first) ? (i32)CRR_ERR_VH_EMPTY : 0;
+        if (completed) cur_ver = L.vh_last_ver;
+        if (rc0) cur_ver = L.current_version;
+        // :123-128 AddOrUpdateItem(NewVersionHistoryItem(event.ID, event.Version)) (versionHistory.go:32-46, :193-226)
+        const i32 vh_rc = (id < 0 || (ver < 0 && ver != CRR_EMPTY_VERSION)) ? (i32)CRR_ERR_VH_INVALID_ITEM
+                          : first ? (G.vh_cap < 1 ? (i32)CRR_ERR_CAPACITY : 0)
+                          : ver < L.vh_last_ver ? (i32)CRR_ERR_VH_LOWER_VERSION
+                          : id <= L.vh_last_id ? (i32)CRR_ERR_VH_EVENT_ID_NOT_INCREASING
+                          : (grow && L.vh_n >= G.vh_cap) ? (i32)CRR_ERR_CAPACITY : 0;
+        rc0 = rc0 ? rc0 : vh_rc;
+        if (rc0) {
+          L.current_version = cur_ver;
+          last_task_step = s - 1;  // the failing event's TaskID is not set (:129 follows the prologue)
+          FAIL(rc0, s);
+        }
+        if (grow) {
+          crr_vh_item* it = G.vh(L.vh_n - 1);
+          it->event_id = L.vh_last_id;
+          it->version = L.vh_last_ver;
+        }
+        L.vh_n += (first || grow) ? 1 : 0;
       }
-      L.vh_n += (first || grow) ? 1 : 0;
+      L.current_version = cur_ver;
       L.vh_last_id = id;
       L.vh_last_ver = ver;
     }
-    last_task_step = s;  // :129 SetLastEventTaskID(event.TaskID): read once, after the loop
 
     // :131-631 the 42-way dispatch.  When every active lane holds the same event type (the
     // common case: histories of one workflow type replay in lockstep) the type is wave-uniform
@@ -4190,7 +4205,10 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
       else
         rc = apply_event(in, out, L, G, T, ev, ps, t, batch_first_id, now_ns,
                          K, retention_days);
-      if (rc) FAIL(rc, s);
+      if (rc) {
+        last_task_step = s;  // :129 SetLastEventTaskID(event.TaskID) has run
+        FAIL(rc, s);
+      }
     }
 
     if (et & CRR_ETYPE_BATCH_LAST) {
@@ -4198,6 +4216,10 @@ __device__ __forceinline__ void replay_body(const crr_inputs& in, const crr_outp
       L.last_first_event_id = batch_first_id;  // :642-643
       L.next_event_id = id + 1;
     }
+  }
+  // :129 SetLastEventTaskID(event.TaskID): a function of the last event applied alone, so not carried
+  // through the loop -- set where a lane leaves it, read once below
+  if (n_ev > 0) last_task_step = n_ev - 1;
   }
   {
     // what the tail reads from HBM -- the last TaskID, the token and rebuild fields of the descriptor --
